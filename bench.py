@@ -19,7 +19,15 @@ replays.  Strong scaling by default (global batch 256 split over the ranks, as n
 `python bench.py --gpus N` launches its own N ranks (one process per GPU, rendezvous on 127.0.0.1); under
 torch.distributed.run (RANK / WORLD_SIZE in the environment) it joins the existing job instead.
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
+A plain run (`--gpus 1 --steps K --warmup W`) does only what the headline needs: build the step, W warm-up steps, K timed steps,
+then ONE JSON line (rank 0) with the contract fields ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", ...)
+and "score_err_trained_weights": the timed engine's all-pairs cosine-score error against the f32 oracle at trained weights (bf16:
+2e-3, outside north_star's 1e-4 -- the headline is BASELINE configs[1]'s stated dtype, the parity engines are beside it).
+--dump-outputs DIR additionally writes what the timed path computed in its last step as DIR/<name>.npy (float32 / float64): infer
+mode "loss" and "embeddings", train mode "loss", "accuracy" and "parameters" (the flat weights after the last Adam update); the
+inputs and weights are seeded, so two builds run with the same arguments can be compared output for output.
+
+--full adds every side measurement below (they take runs of their own) to the same line:
   "roofline"     : the dominant kernel (conv_gemm128x256_ring_kernel, the LDS-DMA conv GEMM, bf16 in / bf16 out -- seven launches
                    per step, 87 % of the forward's flops): every shape replayed back to back between HIP events on the launching
                    stream, against the dense bf16 MFMA peak; "traffic" = HBM bytes per launch from the committed PMC passes
@@ -31,8 +39,6 @@ Prints ONE JSON line (rank 0) with the driver's contract fields plus
   "parity_engine_x3" : the same step on the SPLIT-PRECISION engine ('float32x3': tensors as split bf16 planes, hi*hi + hi*lo + lo*hi on the
                    bf16 matrix cores) -- the engine that meets the 1e-4 score bar at trained weights at matrix-core speed -- with its
                    fraction of the 833 TFLOP/s (= bf16 peak / 3) it is bound by; "parity_engine_f32": the exact-f32 matrix cores (157 TFLOP/s);
-  "score_err_trained_weights" : the timed engine's all-pairs cosine-score error against the f32 oracle at trained weights (bf16: 2e-3,
-                   outside north_star's 1e-4 -- the headline is BASELINE configs[1]'s stated dtype, the parity engines are beside it);
   "single_stream_ms" : the same step as one launch sequence; "clocks": rocm-smi before / after the timed region;
   "cpu_baseline" : the CPU oracle (reference algorithm restated on NumPy + PyTorch-CPU fp32 -- NOT the PaddlePaddle
                    binary) timed on this host's cores on a bounded sample;
@@ -76,6 +82,32 @@ def conv_family_shapes(T):
         s += [(512, 512, 1, 1, ('ysplit',)), (512, 512, 1, 1, ('psum',))]        # tdnn1, tdnn2 of each SE-Res2 block
     s += [(1536, 1536, 1, 1, ('psum', 'psumsq')), (1536, 128, 1, 1, ('rowbias', 'tanh'))]   # MFA, ASP attention TDNN
     return s
+
+
+DUMP_BUDGET_BYTES = 64 << 20      # --dump-outputs: all files together
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: each tensor of `arrays` as <outdir>/<name>.npy, float64 kept, everything else as float32.  The smallest arrays
+    are written whole; one that does not fit its share of DUMP_BUDGET_BYTES is written as a fixed sample of its flattened elements
+    (ascending indices drawn with a constant seed: the same elements for the same shape, run after run)."""
+    os.makedirs(outdir, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        if torch.is_tensor(t):
+            t = t.detach()
+            t = (t if t.dtype == torch.float64 else t.float()).cpu()
+        a = np.asarray(t)
+        host[name] = np.array(a, dtype=np.float64 if a.dtype == np.float64 else np.float32, order='C')
+    left = DUMP_BUDGET_BYTES - 4096 * len(host)            # (room for the .npy headers)
+    for i, name in enumerate(sorted(host, key=lambda k: host[k].nbytes)):
+        a = host[name]
+        share = left // (len(host) - i)
+        if a.nbytes > share:
+            idx = np.sort(np.random.RandomState(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        left -= a.nbytes
+        np.save(os.path.join(outdir, name + '.npy'), a)
 
 
 PMC_FILE = os.path.join(ROOT, 'profiles', 'r06_pmc_infer.json')
@@ -365,7 +397,7 @@ def run_dry(args, rank, world, dist):
     from ppvector.train.ddp import allreduce_mean_
     dev = torch.device('cpu')
     grad = torch.full((1 << 18,), float(rank + 1))
-    a = torch.randn(128, 128)
+    a = torch.randn(128, 128, generator=torch.Generator().manual_seed(0))      # seeded: --dump-outputs compares runs
 
     def step():
         b = a @ a
@@ -374,7 +406,9 @@ def run_dry(args, rank, world, dist):
             allreduce_mean_(grad, bucket_bytes=1 << 18)
         return b.sum()
 
-    dt, _ = run_timed(step, args.steps, args.warmup, dist, dev)
+    dt, res = run_timed(step, args.steps, args.warmup, dist, dev)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {'result': res, 'grad': grad})
     ranks = measured_ranks(dist, dev) if dist is not None else 1
     if rank == 0:
         expect = (world + 1) / 2.0
@@ -467,21 +501,23 @@ def run_infer(args, rank, local_rank, world, dist):
     # (the clock query spawns rocm-smi and takes a few hundred ms: it is taken BEFORE the step is built -- between the graph's last
     # replay and the warm-up steps it left the GPU idle long enough to drop its power state, and W = 5 steps = 6 ms do not bring it
     # back: 1.277 ms per step against 1.236 ms after W = 50, same box, same session)
-    clocks = [gpu_clocks(local_rank)] if rank == 0 else None
+    clocks = [gpu_clocks(local_rank)] if rank == 0 and args.full else None
     run, info = make_infer_step(dev, args.dtype, args.streams, wav, labels, graph=bool(args.graph))
     args.graph = int(info['graph'])
     state, head_w = info['state'], info['head_w']
     want16 = args.dtype == 'bfloat16'
 
     dt, loss = run_timed(run, args.steps, args.warmup, dist, dev)
-    if rank == 0:
+    if rank == 0 and args.dump_outputs:     # before anything else runs on the GPU (under a graph both are its static buffers)
+        dump_outputs(args.dump_outputs, {'loss': loss, 'embeddings': info['emb']})
+    if rank == 0 and args.full:
         clocks.append(gpu_clocks(local_rank))
     loss_v = float(loss)
     assert np.isfinite(loss_v)
     value = world * BATCH * args.steps / dt
     # the same step as ONE launch sequence (no second stream), same K and W: what the concurrent sequences buy on THIS box
     single_ms = None
-    if args.streams > 1 and world == 1:
+    if args.full and args.streams > 1 and world == 1:
         run1, _ = make_infer_step(dev, args.dtype, 1, wav, labels, graph=bool(args.graph),
                                   parts=(info['fz'], info['model'], info['head'], info['state'], info['head_w']))
         dt1, _ = run_timed(run1, args.steps, args.warmup, None, dev)
@@ -489,7 +525,7 @@ def run_infer(args, rank, local_rank, world, dist):
     # the SAME two-sequence step under the protocol of rounds 1-3 (report both): a freshly captured graph with NO pre-replays,
     # timed right behind an idle gap like the one the clock query used to leave -- W warm-up + K timed steps, nothing else
     cold_ms = None
-    if args.graph and world == 1:
+    if args.full and args.graph and world == 1:
         import time as _time
         _time.sleep(0.6)
         run0, info0 = make_infer_step(dev, args.dtype, args.streams, wav, labels, graph=True, prereplays=0,
@@ -514,7 +550,7 @@ def run_infer(args, rank, local_rank, world, dist):
             return {'error': f'{type(e).__name__}: {e}'[:200]}
 
     f32_eng = x3_eng = None
-    if want16 and world == 1 and not args.no_roofline:
+    if args.full and want16 and world == 1 and not args.no_roofline:
         x3_eng = side_engine('float32x3', PEAK_X3_TFLOPS, 'split precision (bf16 hi + lo operands, three MFMAs per product, f32 accumulate); '
                              'all-pairs cosine scores within 1e-4 of the CPU oracle at random-init AND trained weights on all five backbones',
                              max(8, args.steps // 2))
@@ -544,18 +580,21 @@ def run_infer(args, rank, local_rank, world, dist):
         'loss': round(loss_v, 5),
         'stage_roofline_frac': round(value / world * ALG_GFLOP_PER_UTT / 1e3 /
                                      {'bfloat16': PEAK_BF16_TFLOPS, 'float32x3': PEAK_X3_TFLOPS, 'float32': PEAK_F32_TFLOPS}[args.dtype], 4),
-        'single_stream_ms': single_ms,
-        'ms_per_step_without_prereplays': cold_ms,
-        'parity_engine_x3': x3_eng,
-        'parity_engine_f32': f32_eng,
-        'clocks': {'before_step_build': clocks[0], 'after_timed_region': clocks[1]} if rank == 0 else None,
     }
+    if args.full:
+        out.update({
+            'single_stream_ms': single_ms,
+            'ms_per_step_without_prereplays': cold_ms,
+            'parity_engine_x3': x3_eng,
+            'parity_engine_f32': f32_eng,
+            'clocks': {'before_step_build': clocks[0], 'after_timed_region': clocks[1]} if rank == 0 else None,
+        })
     # the path that COMMUNICATES, measured in the same job: the data-parallel training step (global batch 256 split over the
     # ranks, gradient all-reduce over RCCL overlapped with backward) -- reported beside the headline line as "dp_train".
     # The headline line above is already complete: if the collective part fails or hangs on this node (a watchdog thread for
     # world > 1: a hung collective cannot be interrupted from Python), rank 0 still prints it, with the failure in "dp_train".
     dp_train, dp_err = None, None
-    if not args.no_train_line:
+    if args.full and not args.no_train_line:
         import threading
 
         def bail(reason):
@@ -607,7 +646,7 @@ def run_infer(args, rank, local_rank, world, dist):
         if dp_x3 is not None:
             out['dp_train_x3'] = {k: dp_x3[k] for k in ('value', 'unit', 'ms_per_step', 'dtype', 'loss', 'stage_roofline_frac', 'stage_roofline_peak', 'steps')
                                   if k in dp_x3}
-    if world == 1 and not args.no_roofline and want16:
+    if args.full and world == 1 and not args.no_roofline and want16:
         # both protocols on one line: "cold" = rounds 1-3 (2 warm + 10 timed launches per shape, taken first), "loaded" = round 4
         # (20 warm + 30 timed: the launches run in the GPU's loaded power state, as inside the step); `frac` stays the loaded number
         cold = roofline_pass(reps=10, warm=2)
@@ -615,14 +654,14 @@ def run_infer(args, rank, local_rank, world, dist):
         out['roofline']['frac_loaded'] = out['roofline']['frac']
         out['roofline']['frac_cold'] = cold['frac']
         out['roofline']['avg_launch_ms_cold'] = cold['avg_launch_ms']
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out['cpu_baseline'] = cpu_baseline(state, head_w)
     print(json.dumps(out), flush=True)
 
 
 def run_train(args, rank, local_rank, world, dist, steps=None, warmup=None, emit=True):
     """The reference's optimisation step over its own object graph (nn.Sequential(backbone, classifier), AAMLoss, flat Adam),
-    data-parallel over the ranks.  Communication is measured three ways: the flat gradient buffer's all-reduce alone, the step
+    data-parallel over the ranks.  With --full, communication is measured three ways: the flat gradient buffer's all-reduce alone, the step
     with the collective (the reported time) and the same step with the collective switched off."""
     from ppvector.loss.aamloss import AAMLoss
     from ppvector.optimizer.adam import Adam
@@ -658,11 +697,13 @@ def run_train(args, rank, local_rank, world, dist, steps=None, warmup=None, emit
     if graphed:
         warmup = max(warmup, 5)             # three eager steps + the capture + one replay stay outside the timed region
     dt, loss = run_timed(step, steps, warmup, dist, dev)
+    if emit and rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {'loss': last['loss'], 'accuracy': last['acc'], 'parameters': opt.flat})
     loss_v = float(loss)
     assert np.isfinite(loss_v)
     ms_step = dt / steps * 1e3
     comm = {}
-    if dist is not None:
+    if dist is not None and args.full:
         ranks = measured_ranks(dist, dev)
         g = opt.grad
         for _ in range(3):
@@ -741,6 +782,11 @@ def main():
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--dry-run', action='store_true', help='CPU / gloo rehearsal of the multi-rank plumbing (tests)')
+    ap.add_argument('--full', action='store_true',
+                    help='add the side measurements to the line: parity engines, roofline, dp_train, cpu_baseline, clocks, single-stream and '
+                         'no-prereplay timings, train-mode communication split (the --no-* options above select among them)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy')
     args = ap.parse_args()
 
     world_env = os.environ.get('WORLD_SIZE')

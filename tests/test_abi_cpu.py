@@ -7,7 +7,6 @@ import re
 import numpy as np
 import pytest
 import torch
-import yaml
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -91,22 +90,20 @@ def test_reference_configs_build(cfg):
     from ppvector.models import build_model
     from ppvector.data_utils.featurizer import AudioFeaturizer
     from ppvector.utils.utils import dict_to_object
-    path = os.path.join('/root/reference/configs', cfg)
-    if os.path.exists(path):        # the reference's own YAML, unmodified, where it is present
-        raw = yaml.safe_load(open(path, encoding='utf-8'))
-    else:                           # same keys, restated (the reference tree does not travel)
-        model = {'ecapa_tdnn.yml': dict(model='EcapaTdnn', model_args=dict(embd_dim=192, pooling_type='ASP',
-                                                                           channels=[512, 512, 512, 512, 1536])),
-                 'tdnn.yml': dict(model='TDNN', model_args=dict(embd_dim=192, pooling_type='ASP')),
-                 'cam++.yml': dict(model='CAMPPlus', model_args=dict(embd_dim=192)),
-                 'resnet_se.yml': dict(model='ResNetSE', model_args=dict(embd_dim=192, pooling_type='ASP')),
-                 'eres2net.yml': dict(model='ERes2Net', model_args=dict(embd_dim=192, m_channels=32)),
-                 'eres2netv2.yml': dict(model='ERes2NetV2', model_args=dict(embd_dim=192, m_channels=32))}[cfg]
-        model['classifier'] = dict(classifier_type='Cosine', num_speakers=2796, num_blocks=0)
-        raw = dict(preprocess_conf=dict(feature_method='Fbank', method_args=dict(sr=16000, n_mels=80)),
-                   model_conf=model,
-                   loss_conf=dict(loss='AAMLoss', loss_args=dict(margin=0.2, scale=32, easy_margin=False,
-                                                                 label_smoothing=0.0)))
+    # the preprocess_conf / model_conf / loss_conf sections of the reference's configs/<cfg>, restated key for key (the reference
+    # tree is not part of this repository); eres2netv2.yml has no reference file and follows eres2net.yml
+    model = {'ecapa_tdnn.yml': dict(model='EcapaTdnn', model_args=dict(embd_dim=192, pooling_type='ASP',
+                                                                       channels=[512, 512, 512, 512, 1536])),
+             'tdnn.yml': dict(model='TDNN', model_args=dict(embd_dim=192, channels=512, pooling_type='ASP')),
+             'cam++.yml': dict(model='CAMPPlus', model_args=dict(embd_dim=192)),
+             'resnet_se.yml': dict(model='ResNetSE', model_args=dict(embd_dim=192, pooling_type='ASP')),
+             'eres2net.yml': dict(model='ERes2Net', model_args=dict(embd_dim=192, m_channels=32)),
+             'eres2netv2.yml': dict(model='ERes2NetV2', model_args=dict(embd_dim=192, m_channels=32))}[cfg]
+    model['classifier'] = dict(classifier_type='Cosine', num_speakers=2796, num_blocks=0)
+    raw = dict(preprocess_conf=dict(feature_method='Fbank', method_args=dict(sr=16000, n_mels=80)),
+               model_conf=model,
+               loss_conf=dict(loss='AAMLoss', loss_args=dict(margin=0.2, scale=32, easy_margin=False, label_smoothing=0.0),
+                              use_margin_scheduler=True, margin_scheduler_args=dict(initial_margin=0.0, final_margin=0.3)))
     configs = dict_to_object(raw)
     fz = AudioFeaturizer(feature_method=configs.preprocess_conf.feature_method,
                          method_args=configs.preprocess_conf.get('method_args', {}))

@@ -6,6 +6,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
@@ -178,6 +179,30 @@ def test_bench_launches_its_own_ranks():
     assert len(lines) == 1, r.stdout
     out = json.loads(lines[0])
     assert out['n_gpus'] == 2 and out['rccl_ranks'] == 2 and out['steps'] == 3 and out['value'] > 0
+
+
+def test_bench_dump_outputs_repeat_run_for_run(tmp_path):
+    """--dump-outputs DIR: after the timed steps the last step's results land in DIR as float32 .npy files, and the same arguments
+    give the same files (seeded inputs).  --dry-run: the writer and the argument plumbing the GPU run uses, on a CPU step."""
+    import json
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT')}
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f'run{i}'
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--dry-run', '--steps', '4', '--warmup', '1',
+                            '--dump-outputs', str(d)], capture_output=True, text=True, timeout=300, env=env)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
+        assert len(lines) == 1, r.stdout
+        out = json.loads(lines[0])
+        assert out['steps'] == 4 and out['ms_per_step'] > 0
+        assert sorted(p.name for p in d.iterdir()) == ['grad.npy', 'result.npy']
+        dumps.append({p.stem: np.load(p) for p in d.iterdir()})
+    for name, a in dumps[0].items():
+        assert a.dtype == np.float32 and np.all(np.isfinite(a)), name
+        np.testing.assert_array_equal(a, dumps[1][name])
+    assert dumps[0]['grad'].shape == (1 << 18,) and np.all(dumps[0]['grad'] == 1.0)
 
 
 def test_reducer_buckets_follow_backward_order():

@@ -173,3 +173,39 @@ def test_featurizer_beside_the_backbone_stays_bit_identical(rig):
         N.lib().vp_conv256_select(prev)
     print(f'[timed path] Fbank beside the backbone: f32 features / bf16 twin / backbone embeddings differing from quiet runs: {bad} of 120 / 120 / 40')
     assert bad == [0, 0, 0], bad
+
+
+def test_plain_bench_run_dumps_the_timed_step(rig, tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` (no --full): the contract line and nothing of the side measurements,
+    and DIR holds the timed step's last loss and embeddings -- bit-identical to the eager single-stream call chain on the same seeded
+    waveforms and weights (rank 0's shard, bench.shard_seed(1000, 0))."""
+    import json
+    import subprocess
+    import sys
+    bench, dev, parts, wavs, labels = rig
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT')}
+    r = subprocess.run([sys.executable, os.path.join(os.path.dirname(bench.__file__), 'bench.py'), '--gpus', '1', '--steps', '7',
+                        '--warmup', '2', '--dump-outputs', str(tmp_path)], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1, r.stdout[-3000:]
+    out = json.loads(lines[0])
+    print(f"[timed path] plain bench line: {out['value']} {out['unit']}, {out['ms_per_step']} ms per step")
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert k in out, k
+    assert out['steps'] == 7 and out['warmup'] == 2 and out['dtype'] == 'bf16' and out['ms_per_step'] > 0
+    assert not {'roofline', 'cpu_baseline', 'dp_train', 'parity_engine_x3', 'clocks'} & set(out)
+    emb_d = np.load(tmp_path / 'embeddings.npy')
+    loss_d = np.load(tmp_path / 'loss.npy')
+    assert emb_d.dtype == np.float32 and emb_d.shape == (B, 192) and loss_d.shape == ()
+    fz, model, head, _, _ = parts['bfloat16']
+    model.eval()
+    wav = torch.from_numpy(bench.synth_waves(B, L, seed=bench.shard_seed(1000, 0))).to(dev)
+    from ppvector.loss.aamloss import AAMLoss
+    crit = AAMLoss(margin=0.2, scale=32, easy_margin=False, label_smoothing=0.0)
+    emb_e = model.engine('bfloat16').forward(fz(wav, want_bf16=True))
+    loss_e = float(crit(head(emb_e), labels))
+    emb_e = emb_e.float().cpu().numpy()
+    print(f'[timed path] dumped loss {float(loss_d):.6f} vs eager {loss_e:.6f}; max |emb diff| {np.abs(emb_d - emb_e).max():.1e}')
+    np.testing.assert_array_equal(emb_d, emb_e)
+    assert float(loss_d) == np.float32(loss_e)

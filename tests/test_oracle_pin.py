@@ -2,11 +2,10 @@
 
 The fixtures hold outputs of the REFERENCE's own model files (ppvector/models/ecapa_tdnn.py,
 tdnn.py, fc.py, loss/aamloss.py) executed through oracle/paddle_shim by oracle/gen_golden.py.
-Where /root/reference is present (build container) the generator's --check mode is re-run too.
+The generator needs the reference's sources, which are not part of this repository: it is run (with --check) by hand
+where they are present, never by the suite.
 """
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -87,13 +86,6 @@ def test_real_speech_fixture(golden_dir):
         emb = om.ecapa_forward(p, torch.from_numpy(g['feats'])).numpy()
     cos = osc.cosine_matrix(emb.astype(np.float64), emb.astype(np.float64))
     assert np.max(np.abs(cos - g['cos'])) < 1e-5
-
-
-@pytest.mark.skipif(not os.path.isdir('/root/reference'), reason='reference sources not on this box')
-def test_regenerate_against_reference_sources():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'oracle', 'gen_golden.py'), '--check'],
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
 
 
 def test_margin_schedule_endpoints():
