@@ -171,7 +171,9 @@ typedef struct {
                                             (~2^-16 relative per product: the reference's 1e-4 score tolerance at 1/3 of the
                                             bf16 rate = 5.3x the exact-f32 rate); 3 = as 2, with `w` ALREADY split: split bf16
                                             planes (VP_HL32) [Cout][Kw], Kw = KW*Cin rounded up to a multiple of 32 with zero
-                                            columns (vp_tdnn_layer.w_hl) -- only x is split while staging                 */
+                                            columns (vp_tdnn_layer.w_hl) -- only x is split while staging.  Other values,
+                                            and 3 with tensors other than f32, are VP_EINVAL.  hl32 tensors use 2 (their
+                                            weights are split planes already); the weight gradient treats 3 as 2          */
 } vp_conv1d_desc;
 
 int vp_conv1d_tiles_m(int B, int T_out);            /* rows of the psum arrays                     */
@@ -305,6 +307,15 @@ int vp_asp_utt_fwd(vp_ctx* ctx, const void* x, int ldx, const vp_tdnn_layer* tdn
  *   h (B*T, att) hl32, w [C][att] F32 (split in registers), x (B*T, ldx) hl32.  att == 128, C and ldx multiples of 32. */
 int vp_res2_chain_x3_fwd(vp_ctx* ctx, const vp_tdnn_layer* layers, int nconv, const void* t1, void* r2, int B, int T, int C,
                          int width, vp_stream stream);
+/* vp_res2_chain_x3_plan: the launch vp_res2_chain_x3_fwd makes for T frames, nconv convs at dilation dil, host only (no device call):
+ *   nsplit time segments of tseg own frames each (a multiple of 16; the last one non-empty), held windows of at most tp frames, a
+ *   dynamic LDS request of lds_bytes = 4 tp 128 + 49 152 + nconv 768 <= 160 KiB.  VP_OK, or VP_EUNSUP (outputs 0) when no count of
+ *   at most 64 segments fits or dil >= T.  Any output pointer may be NULL.
+ * vp_ecapa_x3_fast_path: 1 when vp_ecapa_fwd of this VP_F32X3 backbone at (B, T) takes the split-plane fast path (every layer's w_hl
+ *   present, T >= 128, B T >= 4096, Res2 width 64 with a plan above, 32-bit offsets), 0 when it takes the generic split-precision path
+ *   or w is not a VP_F32X3 backbone.  Host only: reads the weight struct's fields, never what its pointers point to. */
+int vp_res2_chain_x3_plan(int T, int nconv, int dil, int* nsplit, int* tseg, int* tp, int* lds_bytes);
+int vp_ecapa_x3_fast_path(const vp_ecapa_weights* w, int B, int T);
 int vp_asp_fused_x3_fwd(vp_ctx* ctx, const void* h, const float* w, const float* bias, const void* x, int ldx, const float* center,
                         int ldc, int B, int T, int C, int att, float eps, float* pooled, vp_stream stream);
 

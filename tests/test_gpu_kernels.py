@@ -576,6 +576,74 @@ def test_conv1d_rejects_bad_shapes(N):
     assert lib.vp_conv1d_fwd(ctx, C.byref(d), N.stream_ptr()) == N.VP_EINVAL
 
 
+def test_conv1d_mfma_mode_contract(N):
+    """vp_conv1d_desc.mfma_bf16: values outside 0..3, and 3 (pre-split weights for the f32-tensor kernel) with hl32 tensors, are
+    VP_EINVAL before any launch -- the output keeps its sentinel; the same descriptors in mode 2 run."""
+    from ppvector.models.utils import pack_hl32
+    lib, ctx = N.lib(), N.ctx(0)
+    B, T, Cin, Cout = 2, 300, 64, 64
+    g = torch.Generator().manual_seed(5)
+    x = torch.randn(B, T, Cin, generator=g)
+    w = torch.randn(Cout, 3 * Cin, generator=g) / (3 * Cin) ** 0.5
+    cases = {'f32': (x.cuda(), w.cuda(), N.VP_F32, 3), 'hl32': (pack_hl32(x).cuda(), pack_hl32(w[:, :Cin].contiguous()).cuda(), N.VP_HL32, 1)}
+    for name, (xd, wd, dt, kw) in cases.items():
+        y = torch.full((B, T, Cout), 7.0, device='cuda')
+        d = N.Conv1dDesc()
+        d.dtype_in = d.dtype_out = dt
+        d.B, d.T_in, d.T_out, d.Cin, d.Cout, d.KW, d.dilation, d.stride = B, T, T, Cin, Cout, kw, 1, 1
+        d.pad_mode, d.pad_left = N.VP_PAD_REFLECT, (kw - 1) // 2
+        d.x, d.ldx, d.w, d.y, d.ldy = xd.data_ptr(), Cin, wd.data_ptr(), y.data_ptr(), Cout
+        for mode in (-1, 4, 7) + ((3,) if dt == N.VP_HL32 else ()):
+            d.mfma_bf16 = mode
+            assert lib.vp_conv1d_fwd(ctx, C.byref(d), N.stream_ptr()) == N.VP_EINVAL, (name, mode)
+            assert b'mfma_bf16' in lib.vp_last_error(ctx), (name, mode, lib.vp_last_error(ctx))
+        torch.cuda.synchronize()
+        assert torch.all(y == 7.0), name                                      # nothing launched
+        d.mfma_bf16 = 2
+        N.check(lib.vp_conv1d_fwd(ctx, C.byref(d), N.stream_ptr()), ctx)
+        torch.cuda.synchronize()
+        assert (y != 7.0).float().mean().item() > 0.99, name                   # (an hl32 word pairs two bf16 halves)
+
+
+@pytest.mark.parametrize('case', [(2, 77, 64, 64, 3, 2), (3, 298, 512, 512, 1, 1)])
+def test_wgrad_mode3_is_split_precision(N, case):
+    """vp_conv1d_wgrad_oik_f32 with mfma_bf16 = 3 (a forward descriptor that carries pre-split weights): bit-identical to mode 2 and
+    within split precision's bound of the float64 weight gradient (a single bf16 pass is ~100x further off); out-of-range modes are
+    VP_EINVAL."""
+    lib, ctx = N.lib(), N.ctx(0)
+    B, T, Cin, Cout, kw, dil = case
+    g = torch.Generator().manual_seed(sum(case) + 17)
+    x = torch.randn(B, T, Cin, generator=g)
+    dz = torch.randn(B, T, Cout, generator=g)
+    xt = x.double().transpose(1, 2)
+    if kw > 1:
+        xt = F.pad(xt, (dil * (kw - 1) // 2,) * 2, mode='reflect')
+    w = torch.zeros(Cout, Cin, kw, dtype=torch.float64, requires_grad=True)
+    (F.conv1d(xt, w, None, dilation=dil).transpose(1, 2) * dz.double()).sum().backward()
+    ref = w.grad
+    xd, dzd = x.cuda(), dz.cuda()
+    out = {}
+    for mode in (2, 3, 1, 4, -1):
+        d = N.Conv1dDesc()
+        d.dtype_in = d.dtype_out = N.VP_F32
+        d.B, d.T_in, d.T_out, d.Cin, d.Cout, d.KW, d.dilation, d.stride = B, T, T, Cin, Cout, kw, dil, 1
+        d.pad_mode, d.pad_left = N.VP_PAD_REFLECT, dil * (kw - 1) // 2
+        d.x, d.ldx, d.mfma_bf16 = xd.data_ptr(), Cin, mode
+        dW = torch.full((Cout, Cin, kw), 7.0, device='cuda')
+        ws = torch.empty(int(lib.vp_conv1d_wgrad_workspace_bytes(C.byref(d))), dtype=torch.uint8, device='cuda')
+        rc = lib.vp_conv1d_wgrad_oik_f32(ctx, C.byref(d), dzd.data_ptr(), Cout, dW.data_ptr(), ws.data_ptr(), ws.numel(), N.stream_ptr())
+        torch.cuda.synchronize()
+        if mode in (4, -1):
+            assert rc == N.VP_EINVAL and torch.all(dW == 7.0), (mode, rc)
+            continue
+        N.check(rc, ctx)
+        out[mode] = dW.double().cpu()
+    rel = {m: ((v - ref).norm() / ref.norm()).item() for m, v in out.items()}
+    print(f'[wgrad mode 3 {case}] rel-L2 vs float64: mode 3 {rel[3]:.2e}, mode 2 {rel[2]:.2e}, one bf16 pass {rel[1]:.2e}')
+    assert torch.equal(out[3], out[2])
+    assert rel[2] < 2e-5 and rel[1] > 30 * rel[2], rel
+
+
 def test_conv1d_activations_past_4gib_run_as_batch_slices(N):
     """BASELINE configs[4] at its per-GPU batch (ERes2Net-large, 128 utterances) has activation tensors past 4 GiB; the conv kernels
     address x through a 32-bit buffer offset, so vp_conv1d_fwd runs such a launch as consecutive batch slices (csrc/conv_gemm.hip) --
@@ -1061,16 +1129,15 @@ def test_res2_chain_kernel_vs_float64(N, B, T, dil):
     assert edge.max().item() < 2.0 ** -7 * scale
 
 
-@pytest.mark.parametrize('B,T,dil', [(3, 28, 2), (2, 298, 2), (2, 298, 3), (5, 298, 4), (2, 400, 4), (4, 17, 2), (3, 33, 4), (2, 600, 3), (1, 2000, 4)])
-def test_res2_chain_x3_kernel_vs_float64(N, B, T, dil):
-    """vp_res2_chain_x3_fwd (split precision, tensors as split bf16 planes, the utterance cut into time segments with recomputed halos)
-    against the float64 Res2NetBlock.forward (ecapa_tdnn.py:36-47) of the values the planes carry -- NO intermediate rounding in the
-    reference: every frame of every slice incl. the reflected boundary frames and the frames on both sides of a segment cut (T = 298:
-    two segments cut at 160; T = 400 / 600: three / four), held to split precision's own error."""
+def _res2_x3_vs_float64(N, B, T, dil, nconv=7, seed=None):
+    """vp_res2_chain_x3_fwd on (B, T, (nconv + 1) * 64) against the float64 Res2NetBlock.forward of the values the planes carry, no
+    intermediate rounding in the reference; every frame of every slice.  Returns (plan, max err, mean err, max |ref|, max err over the
+    frames within H = nconv * dil of a segment cut or None when the plan has one segment)."""
     from ppvector.models.utils import pack_hl32, unpack_hl32
     lib, ctx = N.lib(), N.ctx(0)
-    Cc, wdt, nconv = 512, 64, 7
-    g = torch.Generator().manual_seed(100 * T + dil)
+    wdt = 64
+    Cc = (nconv + 1) * wdt
+    g = torch.Generator().manual_seed(100 * T + dil if seed is None else seed)
     t1d = pack_hl32(torch.randn(B, T, Cc, generator=g)).cuda()
     t1 = unpack_hl32(t1d).double().cpu()
     ws = [torch.randn(wdt, wdt, 3, generator=g) / (3 * wdt) ** 0.5 for _ in range(nconv)]
@@ -1092,16 +1159,97 @@ def test_res2_chain_x3_kernel_vs_float64(N, B, T, dil):
         ref[:, :, (j + 1) * wdt:(j + 2) * wdt] = v
         if j + 1 < nconv:
             cur = v + t1[:, :, (j + 2) * wdt:(j + 3) * wdt]
+    plan = [C.c_int() for _ in range(4)]
+    assert lib.vp_res2_chain_x3_plan(T, nconv, dil, *[C.byref(v) for v in plan]) == N.VP_OK, (T, nconv, dil)
+    plan = tuple(v.value for v in plan)
     r2 = pack_hl32(torch.full((B, T, Cc), 7.0)).cuda()
     N.check(lib.vp_res2_chain_x3_fwd(ctx, layers, nconv, t1d.data_ptr(), r2.data_ptr(), B, T, Cc, wdt, N.stream_ptr()), ctx)
     torch.cuda.synchronize()
     out = unpack_hl32(r2).double().cpu()
     assert torch.all(out[:, :, :wdt] == 7.0)                                  # slice 0 belongs to the producing conv
     err = (out[:, :, wdt:] - ref[:, :, wdt:]).abs()
-    scale = ref.abs().max().item()
-    print(f'[res2_chain_x3 B={B} T={T} d={dil}] max err {err.max().item():.3e} (max |ref| {scale:.2f}), mean {err.mean().item():.2e}')
-    assert err.max().item() < 1e-4 * max(1.0, scale), err.max().item()         # seven chained convs of ~2^-17 products + hl32 stores
-    assert err.mean().item() < 1e-5 * max(1.0, scale)
+    ns, ts, H = plan[0], plan[1], nconv * dil
+    near = sorted({t for s in range(1, ns) for t in range(max(0, s * ts - H), min(T, s * ts + H))})
+    cut = err[:, near].max().item() if near else None
+    return plan, err.max().item(), err.mean().item(), ref.abs().max().item(), cut
+
+
+def _res2_x3_check(N, B, T, dil, nconv=7, seed=None):
+    plan, emax, emean, scale, cut = _res2_x3_vs_float64(N, B, T, dil, nconv, seed)
+    bound = 1e-4 * max(1.0, scale)                                      # nconv chained convs of ~2^-17 products + hl32 stores
+    cuts = f'{cut:.3e}' if cut is not None else '-'
+    print(f'[res2_chain_x3 B={B} T={T} d={dil} nconv={nconv} nsplit={plan[0]} tseg={plan[1]} tp={plan[2]}] max err {emax:.3e} '
+          f'(max |ref| {scale:.2f}, bound {bound:.1e}), mean {emean:.2e}, max within H of a cut {cuts}')
+    assert emax < bound, emax
+    assert emean < 1e-5 * max(1.0, scale), emean
+    assert cut is None or cut < bound, cut                              # a short halo cannot hide in the mean
+    return plan, emax, cut
+
+
+@pytest.mark.parametrize('B,T,dil', [(3, 28, 2), (2, 298, 2), (2, 298, 3), (5, 298, 4), (2, 400, 4), (4, 17, 2), (3, 33, 4), (2, 600, 3), (1, 2000, 4)])
+def test_res2_chain_x3_kernel_vs_float64(N, B, T, dil):
+    """vp_res2_chain_x3_fwd (split precision, tensors as split bf16 planes, the utterance cut into time segments with recomputed halos)
+    against the float64 Res2NetBlock.forward (ecapa_tdnn.py:36-47) of the values the planes carry -- NO intermediate rounding in the
+    reference: every frame of every slice incl. the reflected boundary frames and the frames on both sides of a segment cut (T = 298:
+    two segments cut at 160; T = 400 / 600: three / four), held to split precision's own error."""
+    _res2_x3_check(N, B, T, dil)
+
+
+def _plan(N, T, nconv, dil):
+    v = [C.c_int() for _ in range(4)]
+    rc = N.lib().vp_res2_chain_x3_plan(T, nconv, dil, *[C.byref(x) for x in v])
+    return tuple(x.value for x in v) if rc == N.VP_OK else None
+
+
+def _res2_x3_sweep_points(N):
+    """(B, T, dil, nconv) of the sweep, derived from the plan: at 7 convs and each of ECAPA's dilations the first T of a segment count
+    and the T before it (6 counts spread from 1 to the largest), a last segment owning 1 frame and one owning dil frames, the first T
+    of the window a planner that stopped early lost, T = 6000 and the largest planned T; at 1 / 3 / 11 / 15 convs one short and one
+    long T.  B = 2 on a few of them (batch-row offsets)."""
+    pts = []
+    for dil in (2, 3, 4):
+        Ts = np.arange(dil + 1, 12289)
+        ns = np.array([(_plan(N, int(t), 7, dil) or (0,))[0] for t in Ts])
+        tmax = int(Ts[ns > 0].max())
+        first = {int(n): int(Ts[np.argmax(ns == n)]) for n in np.unique(ns[ns > 0])}
+        counts = sorted(first)
+        pick = sorted({counts[int(round(i * (len(counts) - 1) / 5))] for i in range(6)})
+        sel = set()
+        for n in pick:
+            sel.add(first[n])
+            if first[n] - 1 > dil:
+                sel.add(first[n] - 1)
+        for own in (1, dil):                                                   # the last segment owns `own` frames
+            for t in range(1000, tmax + 1):
+                p = _plan(N, t, 7, dil)
+                if p and p[0] > 1 and t - (p[0] - 1) * p[1] == own:
+                    sel.add(t)
+                    break
+        sel |= {{4: 1585, 3: 1921, 2: 2289}[dil], 6000, tmax}
+        pts += [(1, t, dil, 7) for t in sorted(sel)]
+    for nconv in (1, 3, 11, 15):
+        long_T = max(t for t in (2000, 4000, 6000) if _plan(N, t, nconv, 4))
+        pts += [(1, 298, 4, nconv), (1, long_T, 4, nconv)]
+    for B, T, dil in ((2, 1585, 4), (2, 2289, 2), (2, 4000, 4)):
+        pts.append((B, T, dil, 7))
+    pts += [(2, 300, 3, 15), (2, 1000, 2, 11)]
+    return pts
+
+
+def test_res2_chain_x3_sweep_vs_float64(N):
+    """vp_res2_chain_x3_fwd against float64 at the T values where a segment planner goes wrong: segment-count transitions, a last
+    segment that owns 1 or dil frames, the windows an early-stopping planner lost, the largest planned T, and Res2 chains of 1, 3,
+    11 and 15 convs (the latter two LDS-limited to 192-frame windows).  The frames within H of every cut are held to the same bound
+    and reported on their own."""
+    pts = _res2_x3_sweep_points(N)
+    assert 40 <= len(pts) <= 100, len(pts)
+    worst, worst_cut = 0.0, 0.0
+    for B, T, dil, nconv in pts:
+        assert _plan(N, T, nconv, dil) is not None, (T, nconv, dil)
+        plan, emax, cut = _res2_x3_check(N, B, T, dil, nconv, seed=T * 131 + dil * 7 + nconv + 1000 * B)
+        worst = max(worst, emax)
+        worst_cut = max(worst_cut, cut or 0.0)
+    print(f'[res2_chain_x3 sweep] {len(pts)} launches: worst max err {worst:.3e}, worst within H of a cut {worst_cut:.3e}')
 
 
 def test_res2_chain_x3_refuses_shapes_it_does_not_cover(N):

@@ -213,11 +213,44 @@ def test_long_utterance_falls_back_to_per_conv_path(ecapa):
         x = torch.randn(B, T, 80, generator=g) * 3.0
         with torch.no_grad():
             ref = om.ecapa_forward(p, x).numpy()
-        for dtype, tol in (('float32', 2e-4), ('float32x3', 4e-4), ('bfloat16', 6e-2)):
+        for dtype, tol in (('float32', 2e-4), ('float32x3', 5e-5), ('bfloat16', 6e-2)):
             emb = ecapa.engine(dtype).forward(x.cuda()).cpu().numpy()
             rel = np.linalg.norm(emb - ref) / np.linalg.norm(ref)
-            print(f'[T={T} {dtype}] rel-L2 {rel:.3e}')
+            path = ' (fast path)' if dtype == 'float32x3' and ecapa.engine(dtype).x3_fast_path(B, T) else ''
+            print(f'[T={T} {dtype}{path}] rel-L2 {rel:.3e}')
             assert rel < tol, (T, dtype, rel)
+
+
+def test_ecapa_split_precision_paths_at_their_cliffs(ecapa):
+    """engine('float32x3') on both sides of each condition that picks its path (csrc/ecapa.hip: ecapa_hl_ok), the path asserted with
+    x3_fast_path before each run, against the oracle in float64: B T = 4096 / 4092 frames, T = 127, T = 1592 (a segment count a planner
+    that stopped at the first empty last segment never reached: generic before, fast now) and T = 4000 at B = 2 (fast) and B = 1
+    (generic) on the same utterance.  Per-utterance rel-L2 and fast vs generic on the shared utterance both < 2e-5 (the paths measure
+    ~2.4e-6 at 3 s)."""
+    p64 = {k: v.double() for k, v in om.ecapa_params(80, seed=1000).items()}
+    eng = ecapa.engine('float32x3')
+
+    def run(x, fast):
+        assert eng.x3_fast_path(*x.shape[:2]) == fast, (x.shape, fast)
+        emb = eng.forward(x.float().cuda()).cpu().double().numpy()
+        with torch.no_grad():
+            ref = om.ecapa_forward(p64, x.double()).numpy()
+        rel = np.linalg.norm(emb - ref, axis=1) / np.linalg.norm(ref, axis=1)
+        print(f'[ecapa float32x3 cliff B={x.shape[0]} T={x.shape[1]} {"fast" if fast else "generic"}] per-utterance rel-L2 vs '
+              f'float64: max {rel.max():.3e}')
+        assert rel.max() < 2e-5, (x.shape, rel.max())
+        return emb
+
+    for B, T, fast in ((32, 128, True), (31, 132, False), (33, 127, False), (3, 1592, True)):
+        g = torch.Generator().manual_seed(7 * T + B)
+        run(torch.randn(B, T, 80, generator=g, dtype=torch.float64).float().double() * 3.0, fast)
+    g = torch.Generator().manual_seed(4000)
+    x = torch.randn(2, 4000, 80, generator=g, dtype=torch.float64).float().double() * 3.0
+    fast = run(x, True)
+    gen = run(x[:1].contiguous(), False)
+    d = np.linalg.norm(fast[0] - gen[0]) / np.linalg.norm(gen[0])
+    print(f'[ecapa float32x3 cliff T=4000] fast (B = 2) vs generic (B = 1) on the same utterance: rel-L2 {d:.3e}')
+    assert d < 2e-5, d
 
 
 def _cfg():

@@ -73,6 +73,9 @@ int vp_conv1d_fwd(vp_ctx* ctx, const vp_conv1d_desc* d, vp_stream stream) {
         (d->dtype_out != VP_F32 && d->dtype_out != VP_BF16 && d->dtype_out != VP_HL32))
         VP_FAIL(ctx, VP_EINVAL, "conv1d: bad dtype");
     if (d->dtype_in == VP_F32 && d->dtype_out == VP_BF16) VP_FAIL(ctx, VP_EUNSUP, "conv1d: f32 -> bf16 not built");
+    // (mode 3 = pre-split weights on the f32-tensor kernel; the hl32 kernels take split weights as they are, in mode 2)
+    if (d->mfma_bf16 < 0 || d->mfma_bf16 > 3) VP_FAIL(ctx, VP_EINVAL, "conv1d: mfma_bf16 %d outside 0..3", d->mfma_bf16);
+    if (d->mfma_bf16 == 3 && (d->dtype_in != VP_F32 || d->dtype_out != VP_F32)) VP_FAIL(ctx, VP_EINVAL, "conv1d: mfma_bf16 = 3 takes f32 tensors");
     const bool hl_in = d->dtype_in == VP_HL32, hl_out = d->dtype_out == VP_HL32;
     if (hl_in || hl_out) {
         // split bf16 planes (vpmi.h: VP_HL32): 32-channel groups; f32 x (split while staging, mfma_bf16 = 2) or hl32 x, hl32 w with hl32 x
@@ -244,7 +247,6 @@ int vp_conv1d_fwd(vp_ctx* ctx, const vp_conv1d_desc* d, vp_stream stream) {
     if (d->dtype_in == VP_BF16 && d->dtype_out == VP_BF16) return vp_conv_launch_bf16_bf16(ctx, &a, bn, mode, st);
     if (d->dtype_in == VP_BF16 && d->dtype_out == VP_F32) return vp_conv_launch_bf16_f32(ctx, &a, bn, mode, st);
     if (d->mfma_bf16 == 3) {                 // split precision with the weights given as split planes, rows padded to 32-element groups
-        if (d->dtype_in != VP_F32 || d->dtype_out != VP_F32) VP_FAIL(ctx, VP_EINVAL, "conv1d: mfma_bf16 = 3 takes f32 tensors");
         a.Kw = (int)wrow;
         return vp_conv_launch_x3w_f32(ctx, &a, bn, mode, st);
     }

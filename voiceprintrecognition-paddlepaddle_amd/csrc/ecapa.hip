@@ -63,7 +63,7 @@ int vp_run_asp(vp_ctx* ctx, const vp_asp_weights& A, int dtc, const void* x, int
         if (!A.tdnn.w_hl) VP_FAIL(ctx, VP_EINVAL, "asp: hl32 input needs the attention TDNN's split weights (w_hl)");
         vp_conv1d_desc d;
         tdnn_desc(d, A.tdnn, VP_F32X3, B, T, T, VP_PAD_REFLECT);
-        d.dtype_in = d.dtype_out = VP_HL32; d.w = A.tdnn.w_hl;
+        d.dtype_in = d.dtype_out = VP_HL32; d.w = A.tdnn.w_hl; d.mfma_bf16 = 2;      // (hl32 weights with hl32 tensors: mode 2)
         d.x = x; d.ldx = ldx; d.xoff = 0; d.rowbias = A.w_ctx ? w.rowbias : nullptr; d.act2 = VP_ACT_TANH;
         d.y = w.h; d.ldy = A.att; d.yoff = 0;
         if ((rc = vp_conv1d_fwd(ctx, &d, st))) return rc;
@@ -177,7 +177,7 @@ int ecapa_fwd_hl(vp_ctx* ctx, const vp_ecapa_weights* w, const void* feats, int 
     vp_conv1d_desc d;
     auto hl_layer = [&](const vp_tdnn_layer& L) {
         tdnn_desc(d, L, VP_F32X3, B, T, T, VP_PAD_REFLECT);
-        d.dtype_in = d.dtype_out = VP_HL32; d.w = L.w_hl;
+        d.dtype_in = d.dtype_out = VP_HL32; d.w = L.w_hl; d.mfma_bf16 = 2;   // (mode 3 names pre-split weights for f32 tensors only)
     };
     // blocks[0]: with split weights present (w_hl = [C][roundup(kw * F, 32)], zero-padded) the taps are laid out as operand rows (im2col
     // into split planes, 127 MB at 256 x 3 s) and the layer runs as a 1x1 GEMM on the LDS-DMA ring; else f32 features in (split while
@@ -187,7 +187,7 @@ int ecapa_fwd_hl(vp_ctx* ctx, const vp_ecapa_weights* w, const void* feats, int 
         const int pad = w->block0.dil * (w->block0.kw - 1) / 2;
         if ((rc = vp_im2col_hl32(ctx, (const float*)feats, B, T, w->block0.cin, w->block0.kw, w->block0.dil, pad, p.im, Kp0, st))) return rc;
         tdnn_desc(d, w->block0, VP_F32X3, B, T, T, VP_PAD_REFLECT);
-        d.dtype_in = d.dtype_out = VP_HL32; d.w = w->block0.w_hl;
+        d.dtype_in = d.dtype_out = VP_HL32; d.w = w->block0.w_hl; d.mfma_bf16 = 2;
         d.Cin = Kp0; d.KW = 1; d.dilation = 1; d.pad_left = 0;
         d.x = p.im; d.ldx = Kp0; d.y = p.cat0; d.ldy = C;
     } else {
@@ -273,6 +273,13 @@ int vp_asp_fused_x3_fwd(vp_ctx* ctx, const void* h, const float* w, const float*
 int vp_se_gate_fwd(vp_ctx* ctx, const float* psum, const float* shift, int B, int T, int C, int H, const float* w1, const float* b1,
                    const float* w2, const float* b2, float* out, vp_stream stream) {
     return vp_se_gate(ctx, psum, shift, B, T, C, H, w1, b1, w2, b2, out, (hipStream_t)stream);
+}
+
+int vp_ecapa_x3_fast_path(const vp_ecapa_weights* w, int B, int T) {
+    if (!w || B <= 0 || T <= 0 || w->dtype != VP_F32X3 || w->n_blocks < 1 || w->n_blocks > VP_MAX_SE_BLOCKS || w->res2_scale < 2 ||
+        w->res2_scale - 1 > VP_MAX_RES2)
+        return 0;
+    return ecapa_hl_ok(w, B, T) ? 1 : 0;
 }
 
 size_t vp_ecapa_workspace_bytes(const vp_ecapa_weights* w, int B, int T) {

@@ -11,7 +11,10 @@
 // after i convs a segment's values are exact on [lo + i dil, hi - i dil) -- still covering its own frames after the last conv.  The halo
 // frames are recomputed by both neighbours (9 - 19 % more MFMA work at T = 298) and never stored.  LDS: act[2][2 groups][TP][128 B]
 // + wts[3 taps][2 groups][64][128 B] (single buffer: a tap's region takes the next conv's weights as soon as every wave holds the
-// tap's fragments in registers) + the per-channel terms.
+// tap's fragments in registers) + the per-channel terms: 4 TP 128 + 49,152 + nconv 768 bytes <= 160 KiB, so the held window TP is at
+// most 208 frames at nconv <= 10 and 192 at 15.  rx_plan takes the fewest segments (<= 64) that fit: at 7 convs (ECAPA's
+// res2net_scale 8) and dilation <= 4 every dil < T <= 9 216 has a plan (T <= 12 288 at dilation 1); at 15 convs and dilation 4,
+// T <= 4 096.  vp_res2_chain_x3_plan (vpmi.h) reports the plan without launching.
 // A 32-channel group of a row is 128 B = [32 hi | 32 lo]: exactly the bf16 kernels' K-stage row, so LDS-DMA pieces (8 rows x 128 B, XOR
 // swizzle on the source chunk), fragment reads (chunk g = hi, chunk 4 + g = lo) and the coalesced copy-out are those of res2_chain.hip.
 // Per conv and wave: taps outermost (16 weight fragments live), up to two 16-frame tiles, 72 MFMAs per tile.
@@ -24,8 +27,12 @@ constexpr int RX_THREADS = 512;
 constexpr int RX_WAVES = RX_THREADS / 64;
 constexpr int RX_ROUNDS = 2;                 // 16-frame tiles per wave: TP <= 256
 constexpr int RX_WT_BYTES = 3 * 2 * RX_W * 128;          // 49,152
-constexpr int RX_TP_MAX = 208;               // 2 x 2 x 208 x 128 + 49,152 + 5,376 = 161,024 B
+constexpr int RX_PRM_BYTES = 3 * RX_W * 4;              // bias, BN scale, BN shift of one conv (f32)
+constexpr int RX_LDS_BYTES = 160 * 1024;                 // per CU; the frame cap follows from it: 208 frames at 7 convs, 192 at 15
+constexpr int RX_MAX_SEG = 64;
 typedef __attribute__((address_space(3))) void* rx_lds_ptr;
+
+struct RxPlan { int nsplit, Tseg, TP, H, lds; };
 
 struct Res2X3Args {
     const char* t1;          // hl32 (B*T, C): tdnn1 output, x_j = channels [j*64, (j+1)*64)
@@ -218,12 +225,19 @@ __global__ __launch_bounds__(RX_THREADS, 1) void res2_x3_kernel(Res2X3Args a) {
     }
 }
 
-// fewest time segments whose frames (own + halos) fit the LDS; nsplit = 0 when none does
-void rx_plan(int T, int H, int& nsplit, int& Tseg, int& TP) {
-    nsplit = 0;
-    for (int ns = 1; ns <= 64 && !nsplit; ++ns) {                      // (20 s of audio = 2 000 frames: 14 segments at dilation 4)
+// fewest time segments (at most 64) that the kernel can run: whole 16-frame tiles of own frames, no empty last segment, dil < Tseg, and
+// the largest held window (own frames + halos) in at most RX_WAVES * RX_ROUNDS tiles with the LDS request -- ping-pong buffers, one
+// conv's weights, the nconv convs' per-channel terms -- within the CU's 160 KiB.  The last segment's size is not monotone in the count
+// (Tseg is rounded up to whole tiles): a count whose last segment would be empty is skipped, not the end of the search.
+bool rx_plan(int T, int nconv, int dil, RxPlan& p) {
+    p = RxPlan{};
+    if (T < 2 || nconv < 1 || nconv > VP_MAX_RES2 || dil < 1 || dil >= T) return false;
+    const int H = nconv * dil;
+    int tp_max = (RX_LDS_BYTES - RX_WT_BYTES - nconv * RX_PRM_BYTES) / (4 * 128) / 16 * 16;
+    if (tp_max > 16 * RX_WAVES * RX_ROUNDS) tp_max = 16 * RX_WAVES * RX_ROUNDS;
+    for (int ns = 1; ns <= RX_MAX_SEG; ++ns) {
         const int ts = ((T + ns - 1) / ns + 15) / 16 * 16;              // own frames per segment, whole tiles
-        if (ns > 1 && (ns - 1) * ts >= T) break;                        // an empty last segment: not a useful cut
+        if ((ns - 1) * ts >= T || dil >= ts) continue;                  // an empty last segment (or dil >= Tseg): try the next count
         int need = 0;
         for (int s = 0; s < ns; ++s) {
             const int o0 = s * ts, o1 = T < o0 + ts ? T : o0 + ts;
@@ -231,8 +245,13 @@ void rx_plan(int T, int H, int& nsplit, int& Tseg, int& TP) {
             need = h - l > need ? h - l : need;
         }
         const int tp = (need + 15) / 16 * 16;
-        if (tp <= RX_TP_MAX && tp / 16 <= RX_WAVES * RX_ROUNDS) { nsplit = ns; Tseg = ts; TP = tp; }
+        if (tp <= tp_max) {
+            p.nsplit = ns; p.Tseg = ts; p.TP = tp; p.H = H;
+            p.lds = 4 * tp * 128 + RX_WT_BYTES + nconv * RX_PRM_BYTES;
+            return true;
+        }
     }
+    return false;
 }
 
 }  // namespace
@@ -247,9 +266,8 @@ bool vp_res2_chain_x3_ok(const vp_tdnn_layer* layers, int nconv, int B, int T, i
         const vp_tdnn_layer& L = layers[j];
         if (L.kw != 3 || L.cin != RX_W || L.cout != RX_W || L.dil != dil || !L.bias || !L.bn_scale || !L.bn_shift || !L.w_hl) return false;
     }
-    int nsplit, Tseg, TP;
-    rx_plan(T, nconv * dil, nsplit, Tseg, TP);
-    return nsplit > 0 && dil < T && dil < Tseg;
+    RxPlan p;
+    return rx_plan(T, nconv, dil, p);
 }
 
 // hl32 in (t1) / hl32 out (r2); weights hl32 [64][192] (vp_tdnn_layer.w_hl).  VP_EUNSUP when the shape is not covered.
@@ -257,10 +275,8 @@ int vp_res2_chain_x3(vp_ctx* ctx, const vp_tdnn_layer* layers, int nconv, const 
                      hipStream_t st) {
     if (width != RX_W || nconv < 1 || nconv > VP_MAX_RES2 || T < 2 || B > 65535 || C % 32) return VP_EUNSUP;
     const int dil = layers[0].dil;
-    const int H = nconv * dil;
-    int nsplit = 0, Tseg = 0, TP = 0;
-    rx_plan(T, H, nsplit, Tseg, TP);
-    if (!nsplit) return VP_EUNSUP;
+    RxPlan p;
+    if (!rx_plan(T, nconv, dil, p)) return VP_EUNSUP;
     Res2X3Args a;
     memset(&a, 0, sizeof(a));
     for (int j = 0; j < nconv; ++j) {
@@ -269,19 +285,27 @@ int vp_res2_chain_x3(vp_ctx* ctx, const vp_tdnn_layer* layers, int nconv, const 
             return VP_EUNSUP;
         a.w[j] = (const char*)L.w_hl; a.bias[j] = L.bias; a.scale[j] = L.bn_scale; a.shift[j] = L.bn_shift;
     }
-    if (dil >= T || dil >= Tseg) return VP_EUNSUP;
-    a.t1 = (const char*)t1; a.r2 = (char*)r2; a.T = T; a.C = C; a.nconv = nconv; a.dil = dil; a.TP = TP; a.Tseg = Tseg; a.H = H;
+    a.t1 = (const char*)t1; a.r2 = (char*)r2; a.T = T; a.C = C; a.nconv = nconv; a.dil = dil; a.TP = p.TP; a.Tseg = p.Tseg; a.H = p.H;
     const unsigned long long t1b = (unsigned long long)B * T * C * 4;
     if (t1b >= 0xffffff00ull || ((reinterpret_cast<uintptr_t>(t1) | reinterpret_cast<uintptr_t>(r2)) & 15)) return VP_EUNSUP;
     a.t1_bytes = (unsigned)t1b;
-    const size_t smem = (size_t)4 * TP * 128 + RX_WT_BYTES + (size_t)nconv * 192 * 4;
     static bool attr_dev[64] = {};
     bool& attr_set = attr_dev[ctx->device & 63];
     if (!attr_set) {
-        VP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(res2_x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        VP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(res2_x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, RX_LDS_BYTES));
         attr_set = true;
     }
-    hipLaunchKernelGGL(res2_x3_kernel, dim3(nsplit, B), dim3(RX_THREADS), smem, st, a);
+    hipLaunchKernelGGL(res2_x3_kernel, dim3(p.nsplit, B), dim3(RX_THREADS), p.lds, st, a);
     VP_LAUNCH_CHECK(ctx, "res2_x3");
     return VP_OK;
+}
+
+extern "C" int vp_res2_chain_x3_plan(int T, int nconv, int dil, int* nsplit, int* tseg, int* tp, int* lds_bytes) {
+    RxPlan p;
+    const bool ok = rx_plan(T, nconv, dil, p);
+    if (nsplit) *nsplit = p.nsplit;
+    if (tseg) *tseg = p.Tseg;
+    if (tp) *tp = p.TP;
+    if (lds_bytes) *lds_bytes = p.lds;
+    return ok ? VP_OK : VP_EUNSUP;
 }

@@ -1522,6 +1522,7 @@ static int wgrad_impl(vp_ctx* ctx, const vp_conv1d_desc* d, const float* dz, int
     if (!ctx || !d || !d->x || !dz || !dW) VP_FAIL(ctx, VP_EINVAL, "wgrad: null argument");
     const bool bf_in = d->dtype_in == VP_BF16;          // x AND dz bf16 in memory (vp_conv1d_wgrad_bf16_oik): bf16 matrix cores only
     if (d->dtype_in != VP_F32 && !bf_in) VP_FAIL(ctx, VP_EUNSUP, "wgrad: f32 or bf16 tensors");
+    if (d->mfma_bf16 < 0 || d->mfma_bf16 > 3) VP_FAIL(ctx, VP_EINVAL, "wgrad: mfma_bf16 %d outside 0..3", d->mfma_bf16);
     const bool two_d = d->KF > 1 || d->F_in > 1 || d->F_out > 1;
     if (two_d && (d->KF < 1 || d->KW % d->KF || d->F_in < 1 || d->F_out < 1 || d->stride_f < 1 || d->pad_mode != VP_PAD_ZERO))
         VP_FAIL(ctx, VP_EINVAL, "wgrad: bad 2-D geometry (zero padding only)");
@@ -1539,7 +1540,9 @@ static int wgrad_impl(vp_ctx* ctx, const vp_conv1d_desc* d, const float* dz, int
     if (S > 256) S = 256;
     if (nbatch > 1 && S > 512 / nbatch) S = 512 / nbatch > 1 ? 512 / nbatch : 1;      // the batch fills the chip: fewer, longer row splits (less to reduce)
     if ((long long)S * 64 > M) S = (int)((M + 63) / 64);
-    const bool x3 = d->mfma_bf16 == 2 && !bf_in;       // split precision (f32 operands): the 128 x 128 kernel, one workgroup per CU
+    // split precision (f32 operands): the 128 x 128 kernel, one workgroup per CU.  Mode 3 (pre-split forward weights) is mode 2 here:
+    // the weights are not an operand of their own gradient
+    const bool x3 = (d->mfma_bf16 == 2 || d->mfma_bf16 == 3) && !bf_in;
     if ((d->mfma_bf16 || bf_in) && nbatch == 1) {
         // The 128 x 128 mixed-precision kernel keeps two workgroups per CU resident.  A grid of 1.5 rounds of them costs two rounds of
         // time with half-empty CUs in the second (a 3 x 3 conv of 32 channels: 3 tiles x 256 splits = 768 workgroups on 512 slots): take the

@@ -162,6 +162,11 @@ class EcapaEngine(_Engine):
         W.fc_b = self._p(m.fc.conv.bias.detach().float() + fw @ sh)
         self.W = W
 
+    def x3_fast_path(self, B, T):
+        """True when forward() of a (B, T) batch takes the split-plane fast path of the 'float32x3' engine (csrc/ecapa.hip:
+        ecapa_hl_ok), False on the generic split-precision path and on the other engines.  Host only: needs no GPU."""
+        return bool(N.lib().vp_ecapa_x3_fast_path(C.byref(self.W), int(B), int(T)))
+
     def _launch(self, xin, emb, slot=0):
         B, T, F = xin.shape
         lib, ctx = N.lib(), N.ctx(xin.device)
