@@ -521,6 +521,61 @@ int vp_eres2net_fwd(vp_ctx* ctx, const vp_eres2net_weights* w, const void* feats
                     void* ws, size_t ws_bytes, vp_stream stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Res2Net backbone forward, eval mode -- replaces Res2Net.forward (models/res2net.py) with Bottle2neck blocks and ASP pooling:
+ * conv 7x7 stride 3 pad 1 (1 -> m) + BN + ReLU + max pool 3x3 stride 2 pad 1 (one kernel), then per block 1x1 -> `scale` chunks ->
+ * 3x3 convs (stride, chained sp + spx[i] in 'normal' blocks) -> concat with the last chunk (passed through, or exclusive 3x3 average
+ * pool in the 'stage' block) -> 1x1 -> BN + residual -> ReLU.  2-D conv weights [Cout][tap*Cin + c], tap = kt*KF + kf, BN folded.
+ * The concat order is [last chunk | sp_0 | ... | sp_{nums-1}] (nums = max(scale - 1, 1)): the host permutes conv1's output rows and
+ * conv3's input columns to it.  Chunk widths are multiples of 8 (the host zero-pads others).  The ASP / Linear weights are permuted
+ * by the host to the engine's channel order f*C + c (reference: c*F + f).
+ * ---------------------------------------------------------------------------------------------- */
+#define VP_MAX_R2N_BLOCKS 32
+#define VP_MAX_R2N_SCALE 8
+
+typedef struct {
+    vp_tdnn_layer conv1;                        /* 1x1 inplanes -> width*scale, BN folded, ReLU */
+    vp_tdnn_layer convs[VP_MAX_R2N_SCALE];      /* [0, nums): 3x3 (kw = 9) width -> width, stride `stride`, BN folded, ReLU */
+    vp_tdnn_layer conv3;                        /* 1x1 width*scale -> planes*4, BN folded */
+    vp_tdnn_layer down;                         /* optional 1x1 stride `stride` + BN */
+    int stride, has_down, stage, width, scale;  /* stage: 1 = 'stage' block (no chaining, pooled last chunk) */
+} vp_r2n_block;
+
+typedef struct {
+    int dtype;                /* VP_F32 | VP_F32X3 | VP_BF16 (as vp_ecapa_weights) */
+    int feat_dim, embd_dim, n_blocks, m_channels;
+    const float* c1_w;        /* [m][49] f32, tap = kt*7 + kf */
+    const float* c1_b;
+    const float* c1_scale;
+    const float* c1_shift;
+    vp_r2n_block blk[VP_MAX_R2N_BLOCKS];
+    vp_asp_weights asp;       /* C = F' * C4 channels */
+    const float* lin_w;       /* [embd][2*C] f32, bn2 and bn3 folded */
+    const float* lin_b;
+} vp_res2net_weights;
+
+size_t vp_res2net_workspace_bytes(const vp_res2net_weights* w, int B, int T);
+/* feats: (B, T, feat_dim) in w->dtype (f32 for VP_F32X3); emb: (B, embd_dim) f32. */
+int vp_res2net_fwd(vp_ctx* ctx, const vp_res2net_weights* w, const void* feats, int B, int T, float* emb,
+                   void* ws, size_t ws_bytes, vp_stream stream);
+/* Kernel doors (tests; vp_res2net_fwd calls the launchers).  Maps are (B, T, F, C) position-major.
+ * vp_res2net_stem_fwd: feats (B, T, F) -> max_pool(relu(bn(conv7x7 s3 p1 + bias))) (B, T", F", C), dtype VP_F32 | VP_BF16 for both;
+ *   w [C][49] f32 (tap = kt*7 + kf); scale / shift NULL = identity.  C % 4 == 0, C <= 256 (a workgroup computes as many channels as its LDS tile holds: 32 of 256 at F = 80).
+ * vp_avgpool3x3_fwd: exclusive 3x3 average pool, stride 1 or 2, pad 1 (the divisor counts only elements inside the map), C channels
+ *   read from columns [xoff, xoff + C) of rows ldx apart, written to columns [yoff, yoff + C) of rows ldy apart; its backward in f32.
+ * vp_maxpool3x3_*: 3x3 stride 2 pad 1 max pool over dense (B, T, F, C) f32, padding excluded; the backward routes each output's
+ *   gradient to the FIRST maximum of its window in row-major scan order (x = the forward input).
+ * Both backward kernels gather over the outputs covering each input element: no atomics, deterministic.
+ * C, ld*, *off multiples of 4. */
+int vp_res2net_stem_fwd(vp_ctx* ctx, int dtype, const void* feats, void* out, const float* w, const float* bias, const float* scale,
+                        const float* shift, int B, int T, int F, int C, vp_stream stream);
+int vp_avgpool3x3_fwd(vp_ctx* ctx, int dtype, const void* x, int ldx, int xoff, void* y, int ldy, int yoff, int B, int T, int F, int C,
+                      int stride, vp_stream stream);
+int vp_avgpool3x3_bwd_f32(vp_ctx* ctx, const float* dy, int lddy, int dyoff, float* dx, int lddx, int dxoff, int B, int T, int F, int C,
+                          int stride, vp_stream stream);
+int vp_maxpool3x3_fwd_f32(vp_ctx* ctx, const float* x, float* y, int B, int T, int F, int C, vp_stream stream);
+int vp_maxpool3x3_bwd_f32(vp_ctx* ctx, const float* x, const float* dy, float* dx, int B, int T, int F, int C, vp_stream stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Cosine classifier + AAM-softmax loss -- replaces SpeakerIdentification.forward 'Cosine' branch
  * (models/fc.py:41-53) and AAMLoss.forward (loss/aamloss.py:28-47) incl. CrossEntropyLoss
  * (label_smoothing, mean reduction).  emb (B, D) f32; W (D, C) f32 (fc.py:31 layout); labels int64.

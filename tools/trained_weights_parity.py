@@ -7,7 +7,7 @@ held-out utterances all-pairs with
     the CPU oracle (f32; oracle/*.py, the restatement pinned on the reference's model files) -- the yardstick,
     the f32 engine, the split-precision ('float32x3') engine and the bf16 engine of this package, eval mode, the same features,
 and prints the largest cosine-score difference of each engine from the oracle.
-    python tools/trained_weights_parity.py [EcapaTdnn|TDNN|CAMPPlus|ResNetSE|ERes2Net] [steps] [batch]"""
+    python tools/trained_weights_parity.py [EcapaTdnn|TDNN|CAMPPlus|ResNetSE|ERes2Net|Res2Net] [steps] [batch]"""
 import math
 import os
 import sys
@@ -33,16 +33,19 @@ from ppvector.models.campplus import CAMPPlus  # noqa: E402
 from ppvector.models.ecapa_tdnn import EcapaTdnn  # noqa: E402
 from ppvector.models.eres2net import ERes2Net  # noqa: E402
 from ppvector.models.fc import SpeakerIdentification  # noqa: E402
+from ppvector.models.res2net import Res2Net  # noqa: E402
 from ppvector.models.resnet_se import ResNetSE  # noqa: E402
 from ppvector.models.tdnn import TDNN  # noqa: E402
 from ppvector.optimizer.adam import Adam  # noqa: E402
 from ppvector.train.step import TrainStep  # noqa: E402
+from tests import res2net_oracle as o2n  # noqa: E402
 
 n_spk, epochs = 64, 10
 FWD = {'CAMPPlus': oc.campplus_forward, 'TDNN': om.tdnn_forward, 'EcapaTdnn': om.ecapa_forward, 'ResNetSE': orse.resnetse_forward,
-       'ERes2Net': oer.eres2net_forward}
+       'ERes2Net': oer.eres2net_forward, 'Res2Net': o2n.res2net_forward}
 MAKE = {'CAMPPlus': lambda: CAMPPlus(80, embd_dim=192), 'TDNN': lambda: TDNN(80), 'EcapaTdnn': lambda: EcapaTdnn(80),
-        'ResNetSE': lambda: ResNetSE(80, embd_dim=192), 'ERes2Net': lambda: ERes2Net(80, embd_dim=192, m_channels=32)}
+        'ResNetSE': lambda: ResNetSE(80, embd_dim=192), 'ERes2Net': lambda: ERes2Net(80, embd_dim=192, m_channels=32),
+        'Res2Net': lambda: Res2Net(80, m_channels=32, embd_dim=192)}
 
 
 def scores(e):

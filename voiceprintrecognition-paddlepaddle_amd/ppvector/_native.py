@@ -152,6 +152,20 @@ class Eres2netWeights(C.Structure):
                 ('seg_w', c_void_p), ('seg_b', c_void_p)]
 
 
+
+VP_MAX_R2N_BLOCKS, VP_MAX_R2N_SCALE = 32, 8
+
+
+class R2nBlock(C.Structure):
+    _fields_ = [('conv1', TdnnLayer), ('convs', TdnnLayer * VP_MAX_R2N_SCALE), ('conv3', TdnnLayer), ('down', TdnnLayer),
+                ('stride', c_int), ('has_down', c_int), ('stage', c_int), ('width', c_int), ('scale', c_int)]
+
+
+class Res2netWeights(C.Structure):
+    _fields_ = [('dtype', c_int), ('feat_dim', c_int), ('embd_dim', c_int), ('n_blocks', c_int), ('m_channels', c_int),
+                ('c1_w', c_void_p), ('c1_b', c_void_p), ('c1_scale', c_void_p), ('c1_shift', c_void_p),
+                ('blk', R2nBlock * VP_MAX_R2N_BLOCKS), ('asp', AspWeights), ('lin_w', c_void_p), ('lin_b', c_void_p)]
+
 _PROTOS = {
     'vp_version': (c_int, []),
     'vp_create': (c_void_p, [c_int]),
@@ -250,6 +264,17 @@ _PROTOS = {
     'vp_eres2net_workspace_bytes': (c_size_t, [C.POINTER(Eres2netWeights), c_int, c_int]),
     'vp_eres2net_fwd': (c_int, [c_void_p, C.POINTER(Eres2netWeights), c_void_p, c_int, c_int, c_void_p, c_void_p,
                                 c_size_t, c_void_p]),
+    'vp_res2net_workspace_bytes': (c_size_t, [C.POINTER(Res2netWeights), c_int, c_int]),
+    'vp_res2net_fwd': (c_int, [c_void_p, C.POINTER(Res2netWeights), c_void_p, c_int, c_int, c_void_p, c_void_p,
+                               c_size_t, c_void_p]),
+    'vp_res2net_stem_fwd': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                    c_int, c_void_p]),
+    'vp_avgpool3x3_fwd': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                  c_void_p]),
+    'vp_avgpool3x3_bwd_f32': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                      c_void_p]),
+    'vp_maxpool3x3_fwd_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    'vp_maxpool3x3_bwd_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     'vp_cosine_logits_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'vp_cosine_logits_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                      c_size_t, c_void_p]),

@@ -1465,7 +1465,7 @@ class SphereFace2Fn(torch.autograd.Function):
 
 
 class Conv2dBlock(torch.autograd.Function):
-    """2-D conv over (B, T, F, C) positions (zero padding (k-1)/2, stride s on both axes) [-> BatchNorm (batch statistics)]
+    """2-D conv over (B, T, F, C) positions (zero padding (k-1)/2 or cfg['pad'], stride s on both axes) [-> BatchNorm (batch statistics)]
     [-> ReLU]: the Conv2D -> BatchNorm2D -> ReLU units of models/resnet_se.py:8-45,72-74 (BN BEFORE the ReLU, unlike TDNNBlock).
     x (B*T*F, Cin) f32, weight (Cout, Cin, kF, kT) as stored by the reference."""
 
@@ -1477,7 +1477,8 @@ class Conv2dBlock(torch.autograd.Function):
         st, sf = cfg.get('stride_t', cfg.get('stride', 1)), cfg.get('stride_f', cfg.get('stride', 1))
         dil = cfg.get('dilation', 1)                       # along time
         Cout, Cin, KF, KT = weight.shape
-        pad, padf = dil * (KT - 1) // 2, (KF - 1) // 2
+        # zero padding: (k - 1) / 2 on each axis unless cfg gives 'pad' (both axes; Res2Net's 7x7 stride-3 stem pads 1)
+        pad, padf = cfg.get('pad', dil * (KT - 1) // 2), cfg.get('pad', (KF - 1) // 2)
         To, Fo = (T + 2 * pad - dil * (KT - 1) - 1) // st + 1, (Fq + 2 * padf - (KF - 1) - 1) // sf + 1
         s = (st, sf, dil, padf)
         act = {None: 0, 'relu': N.VP_ACT_RELU, 'hardtanh': N.VP_ACT_HARDTANH20, 'silu': N.VP_ACT_SILU, 'tanh': N.VP_ACT_TANH}[
