@@ -10,7 +10,8 @@
 // at pack time).  The DenseNet-style concat is ONE (B*T', Cmax) buffer per block: layer i reads
 // columns [0, C_i) through the conv GEMM's input prologue (its own BN + ReLU applied while staging)
 // and writes its 32 new channels in place -- none of the reference's 52 concat copies exist.
-#include "common.h"
+// Descriptors are built by launch.h (vp_layer_desc + geometry); a call site sets only what is its own.
+#include "launch.h"
 
 namespace {
 
@@ -212,16 +213,6 @@ __global__ __launch_bounds__(256) void bn_relu_stats_kernel(StatArgs<T> a) {
     }
 }
 
-struct Carver {
-    char* base; size_t off;
-    explicit Carver(void* p) : base((char*)p), off(0) {}
-    void* take(size_t bytes) {
-        size_t o = off;
-        off += vp_align_up(bytes ? bytes : 1, 256);
-        return base ? (void*)(base + o) : nullptr;
-    }
-};
-
 struct CamPlan {
     void *fa, *fb, *fc;                 // FCM ping-pong (B,T,F,32)
     void *cat[2];                       // D-TDNN concat buffers (B*T', Cmax)
@@ -231,11 +222,9 @@ struct CamPlan {
     int Tn, Cmax, nseg;
 };
 
-int cam_Tn(int T) { return (T - 1) / 2 + 1; }          // k5 s2 pad 2
-
 void plan_cam(const vp_campplus_weights* w, int B, int T, void* ws, CamPlan& p) {
     const size_t es = vp_dtype_size(w->dtype);
-    p.Tn = cam_Tn(T);
+    p.Tn = vp_down2(T);                       // k5 s2 pad 2
     int ch = w->init_channels, cmax = ch;
     for (int b = 0; b < w->n_blocks; ++b) {
         ch += w->block_layers[b] * w->growth;
@@ -260,16 +249,12 @@ void plan_cam(const vp_campplus_weights* w, int B, int T, void* ws, CamPlan& p) 
     p.total = c.off;
 }
 
+// FCM convs: 3x3 pad 1 (kw == 9) or 1x1 over (B, T, F, .), strided on the frequency axis only (not vp_geom2d's both axes)
 void conv2d_desc(vp_conv1d_desc& d, const vp_tdnn_layer& L, int dt, int B, int T, int F_in, int F_out, int stride_f) {
-    memset(&d, 0, sizeof(d));
-    vp_desc_dtype(d, dt); d.B = B; d.T_in = T; d.T_out = T;
-    d.Cin = L.cin; d.Cout = L.cout; d.KW = L.kw; d.dilation = 1; d.stride = 1;
+    vp_layer_desc(d, L, dt, VP_PAD_ZERO); vp_geom_rows(d, B, T, T);
     d.KF = L.kw == 9 ? 3 : 1;
-    d.pad_left = L.kw == 9 ? 1 : 0; d.pad_f = L.kw == 9 ? 1 : 0; d.pad_mode = VP_PAD_ZERO;
+    d.pad_left = L.kw == 9 ? 1 : 0; d.pad_f = L.kw == 9 ? 1 : 0;
     d.F_in = F_in; d.F_out = F_out; d.stride_f = stride_f;
-    d.ldx = L.cin; d.ldy = L.cout;
-    vp_desc_weights(d, L);
-    d.bias = L.bias; d.bn_scale = L.bn_scale; d.bn_shift = L.bn_shift;
 }
 
 }  // namespace
@@ -366,7 +351,7 @@ int vp_campplus_fwd(vp_ctx* ctx, const vp_campplus_weights* w, const void* feats
     void* t2 = p.fc;
     for (int i = 0; i < 4; ++i) {
         const vp_resblock& R = w->res[i];
-        const int Fo = R.stride == 2 ? (F - 1) / 2 + 1 : F;
+        const int Fo = vp_down(F, R.stride);
         // a stride-1 block with the identity shortcut: both convs and the residual in one launch (h stays in LDS)
         if (dt == VP_BF16 && !R.has_shortcut && R.stride == 1) {
             const int fr = vp_resblock_c32_bf16(ctx, cur, t2, &R.conv1, &R.conv2, B, T, F, st);
@@ -411,7 +396,7 @@ int vp_campplus_fwd(vp_ctx* ctx, const vp_campplus_weights* w, const void* feats
         F = Fo;
     }
     {
-        const int Fo = (F - 1) / 2 + 1;
+        const int Fo = vp_down2(F);
         int fast = VP_EUNSUP;
         if (dt == VP_BF16) fast = vp_conv3x3_c32_bf16(ctx, cur, t1, &w->fcm_conv2, nullptr, 1, nullptr, nullptr, B, T, F, 2, nullptr, nullptr, nullptr, nullptr, nullptr, st);
         if (fast != VP_OK && fast != VP_EUNSUP) return fast;
@@ -427,11 +412,10 @@ int vp_campplus_fwd(vp_ctx* ctx, const vp_campplus_weights* w, const void* feats
 
     // ---- TDNN: conv k5 stride 2 zero-pad 2 -> BN -> ReLU, into columns [0, init) of cat[0]
     const int Tn = p.Tn, ld = p.Cmax;
-    memset(&d, 0, sizeof(d));
-    vp_desc_dtype(d, dtc); d.B = B; d.T_in = T; d.T_out = Tn; d.Cin = Cf; d.Cout = w->tdnn.cout;
-    d.KW = w->tdnn.kw; d.dilation = 1; d.stride = 2; d.pad_left = (w->tdnn.kw - 1) / 2; d.pad_mode = VP_PAD_ZERO;
-    d.x = t1; d.ldx = Cf; vp_desc_weights(d, w->tdnn); d.bias = w->tdnn.bias; d.bn_scale = w->tdnn.bn_scale; d.bn_shift = w->tdnn.bn_shift;
-    d.act2 = VP_ACT_RELU; d.y = p.cat[0]; d.ldy = ld;
+    vp_layer_desc(d, w->tdnn, dtc, VP_PAD_ZERO);             // (cin == Cf: checked above)
+    vp_geom_rows(d, B, T, Tn);
+    d.stride = 2; d.pad_left = (w->tdnn.kw - 1) / 2;
+    d.x = t1; d.act2 = VP_ACT_RELU; d.y = p.cat[0]; d.ldy = ld;
     if ((rc = vp_conv1d_fwd(ctx, &d, st))) return rc;
 
     // ---- D-TDNN blocks
@@ -448,11 +432,10 @@ int vp_campplus_fwd(vp_ctx* ctx, const vp_campplus_weights* w, const void* feats
         for (int l = 0; l < w->block_layers[b] && fused != VP_OK; ++l, ++li) {
             const vp_cam_layer& L = w->layers[li];
             // h2 = relu(bn2(linear1(relu(bn1(x[:, :ch])))))  -- bn1+relu is the conv's input prologue
-            memset(&d, 0, sizeof(d));
-            vp_desc_dtype(d, dtc); d.B = B; d.T_in = Tn; d.T_out = Tn; d.Cin = ch; d.Cout = bnc; d.KW = 1;
-            d.dilation = 1; d.stride = 1; d.pad_mode = VP_PAD_ZERO;
-            d.x = cat; d.ldx = ld; vp_desc_weights(d, L.linear1); d.bias = L.linear1.bias; d.pro_scale = L.bn1_scale; d.pro_shift = L.bn1_shift;
-            d.bn_scale = L.linear1.bn_scale; d.bn_shift = L.linear1.bn_shift; d.act2 = VP_ACT_RELU; d.y = p.h2; d.ldy = bnc;
+            vp_layer_desc(d, L.linear1, dtc, VP_PAD_ZERO); vp_geom_rows(d, B, Tn, Tn);
+            d.Cin = ch; d.Cout = bnc; d.KW = 1;             // the running channel count and the block's widths, not the layer's
+            d.x = cat; d.ldx = ld; d.pro_scale = L.bn1_scale; d.pro_shift = L.bn1_shift;
+            d.act2 = VP_ACT_RELU; d.y = p.h2; d.ldy = bnc;
             if ((rc = vp_conv1d_fwd(ctx, &d, st))) return rc;
             // context gate m = sigmoid(W2 relu(W1 (mean + segmean) + b1) + b2), one row per (utterance, segment)
             {
@@ -475,7 +458,8 @@ int vp_campplus_fwd(vp_ctx* ctx, const vp_campplus_weights* w, const void* feats
                 }
                 VP_LAUNCH_CHECK(ctx, "cam_gate");
             }
-            // y = linear_local(h2) * m, written in place as the layer's new channels
+            // y = linear_local(h2) * m, written in place as the layer's new channels (open-coded: bias only, the layer's BN
+            // fields are not read, and the one dilated site here)
             memset(&d, 0, sizeof(d));
             vp_desc_dtype(d, dtc); d.B = B; d.T_in = Tn; d.T_out = Tn; d.Cin = bnc; d.Cout = gr;
             d.KW = L.local.kw; d.dilation = L.local.dil; d.stride = 1; d.pad_left = L.local.dil * (L.local.kw - 1) / 2;
@@ -484,7 +468,7 @@ int vp_campplus_fwd(vp_ctx* ctx, const vp_campplus_weights* w, const void* feats
             if ((rc = vp_conv1d_fwd(ctx, &d, st))) return rc;
             ch += gr;
         }
-        // transit: linear(relu(bn(x))) -> ch/2, into the other concat buffer
+        // transit: linear(relu(bn(x))) -> ch/2, into the other concat buffer (open-coded: bias only, the layer's BN fields are not read)
         const vp_transit& Tr = w->transit[b];
         memset(&d, 0, sizeof(d));
         vp_desc_dtype(d, dtc); d.B = B; d.T_in = Tn; d.T_out = Tn; d.Cin = ch; d.Cout = ch / 2; d.KW = 1;

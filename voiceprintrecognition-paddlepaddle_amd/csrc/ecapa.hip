@@ -12,33 +12,21 @@
 // Three arithmetic modes per backbone (`dtype` of the weights struct): VP_F32 exact f32 matrix cores; VP_BF16 bf16 tensors with the fused
 // bf16 kernels; VP_F32X3 split precision -- f32 tensors on the generic kernels, or, for ECAPA with split weights present, tensors as
 // split bf16 planes on the LDS-DMA ring / fused hl32 kernels (ecapa_fwd_hl below).
-#include "common.h"
+// Descriptors are built by launch.h (vp_layer_desc + geometry); tdnn_desc below adds what the 1-D TDNN layers share.
+#include "launch.h"
 
 #include <stdlib.h>
 
 namespace {
 
-struct Carver {
-    char* base; size_t off; size_t cap;
-    Carver(void* p, size_t c) : base((char*)p), off(0), cap(c) {}
-    void* take(size_t bytes) {
-        size_t o = off;
-        off += vp_align_up(bytes ? bytes : 1, 256);
-        return base ? (void*)(base + o) : nullptr;
-    }
-};
-
+// a TDNN layer conv -> ReLU -> BN with the layer's dilation, 'same' padding unless pad_mode is VP_PAD_NONE.  Every caller sets the
+// tensors and their row strides (ldx / ldy) itself: inputs and outputs are mostly column slices of wider buffers.
 void tdnn_desc(vp_conv1d_desc& d, const vp_tdnn_layer& L, int dtype, int B, int T_in, int T_out, int pad_mode) {
-    memset(&d, 0, sizeof(d));
-    vp_desc_dtype(d, dtype);
-    d.B = B; d.T_in = T_in; d.T_out = T_out;
-    d.Cin = L.cin; d.Cout = L.cout; d.KW = L.kw; d.dilation = L.dil; d.stride = 1;
-    d.pad_mode = pad_mode;
-    d.pad_left = pad_mode == VP_PAD_NONE ? 0 : L.dil * (L.kw - 1) / 2;
-    vp_desc_weights(d, L);
-    d.bias = L.bias; d.act = VP_ACT_RELU; d.bn_scale = L.bn_scale; d.bn_shift = L.bn_shift;
+    vp_layer_desc(d, L, dtype, pad_mode);
+    vp_geom_rows(d, B, T_in, T_out);
+    d.dilation = L.dil; d.pad_left = pad_mode == VP_PAD_NONE ? 0 : L.dil * (L.kw - 1) / 2;
+    d.act = VP_ACT_RELU; d.ldx = d.ldy = 0;
 }
-
 
 }  // namespace
 
@@ -86,7 +74,7 @@ int vp_run_asp(vp_ctx* ctx, const vp_asp_weights& A, int dtc, const void* x, int
         rc = vp_asp_fused_bf16(ctx, w.h, A.conv_w, A.conv_b, x, ldx, w.stats, 2 * C, B, T, C, A.att, 1e-12f, w.pooled, st);
         if (rc != VP_EUNSUP) return rc;
     }
-    memset(&d, 0, sizeof(d));
+    memset(&d, 0, sizeof(d));              // (open-coded: the logits conv has no vp_tdnn_layer, only its weights and bias)
     vp_desc_dtype(d, dtc);
     d.dtype_out = VP_F32; d.B = B; d.T_in = T; d.T_out = T; d.Cin = A.att; d.Cout = C;
     d.KW = 1; d.dilation = 1; d.stride = 1; d.pad_mode = VP_PAD_REFLECT; d.pad_left = 0;
@@ -104,14 +92,14 @@ struct EcapaPlan {
     size_t total;
 };
 
-int plan_ecapa(const vp_ecapa_weights* w, int B, int T, void* ws, size_t cap, EcapaPlan& p) {
+int plan_ecapa(const vp_ecapa_weights* w, int B, int T, void* ws, EcapaPlan& p) {
     const size_t es = vp_dtype_size(w->dtype);
     const size_t M = (size_t)B * T;
     const int C = w->block0.cout, Cm = w->mfa.cout, nb = w->n_blocks;
     const int width = C / w->res2_scale;
     const int cmax = C > Cm ? C : Cm;
     const size_t nps = (size_t)vp_conv1d_tiles_m(B, T) * vp_conv1d_nseg(T) * cmax * sizeof(float);
-    Carver c(ws, cap);
+    Carver c(ws);
     p.cat0 = c.take(M * C * es);
     p.cat = c.take(M * (size_t)nb * C * es);
     p.t1 = c.take(M * C * es);
@@ -285,7 +273,7 @@ int vp_ecapa_x3_fast_path(const vp_ecapa_weights* w, int B, int T) {
 size_t vp_ecapa_workspace_bytes(const vp_ecapa_weights* w, int B, int T) {
     if (!w || B <= 0 || T <= 0) return 0;
     EcapaPlan p;
-    plan_ecapa(w, B, T, nullptr, 0, p);
+    plan_ecapa(w, B, T, nullptr, p);
     return p.total;
 }
 
@@ -295,7 +283,7 @@ int vp_ecapa_fwd(vp_ctx* ctx, const vp_ecapa_weights* w, const void* feats, int 
     int rc = check_ecapa(ctx, w);
     if (rc) return rc;
     EcapaPlan p;
-    plan_ecapa(w, B, T, ws, ws_bytes, p);
+    plan_ecapa(w, B, T, ws, p);
     if (!ws || ws_bytes < p.total) VP_FAIL(ctx, VP_EWORKSPACE, "ecapa: workspace %zu < %zu", ws_bytes, p.total);
     hipStream_t st = (hipStream_t)stream;
     const int dtc = w->dtype, dt = vp_storage_dtype(dtc);
@@ -370,13 +358,13 @@ static void tdnn_T(const vp_tdnn_weights* w, int T, int Ts[6]) {
 
 struct TdnnPlan { void* a; void* b; void* h; float *e, *psum, *psumsq, *stats, *rowbias, *pooled; size_t total; };
 
-static void plan_tdnn(const vp_tdnn_weights* w, int B, int T, void* ws, size_t cap, TdnnPlan& p) {
+static void plan_tdnn(const vp_tdnn_weights* w, int B, int T, void* ws, TdnnPlan& p) {
     const size_t es = vp_dtype_size(w->dtype);
     const int C = w->channels;
     int Ts[6];
     tdnn_T(w, T, Ts);
     const int T1 = Ts[1] > 0 ? Ts[1] : 1, T5 = Ts[5] > 0 ? Ts[5] : 1;
-    Carver c(ws, cap);
+    Carver c(ws);
     p.a = c.take((size_t)B * T1 * C * es);
     p.b = c.take((size_t)B * T1 * C * es);
     p.h = c.take((size_t)B * T5 * w->asp.att * es);
@@ -393,7 +381,7 @@ static void plan_tdnn(const vp_tdnn_weights* w, int B, int T, void* ws, size_t c
 size_t vp_tdnn_workspace_bytes(const vp_tdnn_weights* w, int B, int T) {
     if (!w || B <= 0 || T <= 0) return 0;
     TdnnPlan p;
-    plan_tdnn(w, B, T, nullptr, 0, p);
+    plan_tdnn(w, B, T, nullptr, p);
     return p.total;
 }
 
@@ -405,7 +393,7 @@ int vp_tdnn_fwd(vp_ctx* ctx, const vp_tdnn_weights* w, const void* feats, int B,
     tdnn_T(w, T, Ts);
     if (Ts[5] < 1) VP_FAIL(ctx, VP_EINVAL, "tdnn: %d frames are fewer than the receptive field", T);
     TdnnPlan p;
-    plan_tdnn(w, B, T, ws, ws_bytes, p);
+    plan_tdnn(w, B, T, ws, p);
     if (!ws || ws_bytes < p.total) VP_FAIL(ctx, VP_EWORKSPACE, "tdnn: workspace %zu < %zu", ws_bytes, p.total);
     hipStream_t st = (hipStream_t)stream;
     const int C = w->channels;

@@ -7,19 +7,12 @@
 // conv (input = a column slice of the previous tensor, output = a column slice of the concat buffer; the Res2 hand-off
 // sp + spx[i] comes out of the previous conv's epilogue as `aux`) -> 1x1 with the residual and the Hardtanh fused.
 // AFF = column copies into a (P, 2C) buffer, two 1x1 GEMMs (SiLU, tanh fused) and one combine pass.
-#include "common.h"
+// Descriptors are built by launch.h (vp_layer_desc + geometry); a call site sets only what is its own.  The position-major GEMMs here
+// run as ONE sequence of all B t f positions (vp_geom_rows(d, 1, P, P)), unlike ResNetSE / Res2Net (B sequences of t f), so the
+// stride-1 shortcut keeps its own form instead of vp_conv1x1_strided.
+#include "launch.h"
 
 namespace {
-
-struct Carver {
-    char* base; size_t off;
-    explicit Carver(void* p) : base((char*)p), off(0) {}
-    void* take(size_t bytes) {
-        size_t o = off;
-        off += vp_align_up(bytes ? bytes : 1, 256);
-        return base ? (void*)(base + o) : nullptr;
-    }
-};
 
 struct ErePlan {
     void *xa, *xb, *o1, *o2, *spin, *cat, *a1, *att, *res;     // block scratch (sized for the largest block)
@@ -30,15 +23,14 @@ struct ErePlan {
     int t[5], f[5];                                            // (T, F) at the stem and after each stage
 };
 
-int down2(int v) { return (v - 1) / 2 + 1; }
 size_t vp_max(size_t a, size_t b) { return a > b ? a : b; }
 
 void plan_ere(const vp_eres2net_weights* w, int B, int T, void* ws, ErePlan& p) {
     const size_t es = vp_dtype_size(w->dtype);
     p.t[0] = T; p.f[0] = w->feat_dim;
     for (int s = 1; s <= 4; ++s) {
-        p.t[s] = s == 1 ? p.t[0] : down2(p.t[s - 1]);
-        p.f[s] = s == 1 ? p.f[0] : down2(p.f[s - 1]);
+        p.t[s] = s == 1 ? p.t[0] : vp_down2(p.t[s - 1]);
+        p.f[s] = s == 1 ? p.f[0] : vp_down2(p.f[s - 1]);
     }
     size_t io = (size_t)B * T * w->feat_dim * w->m_channels, mid = 0, sp = 0, cat = 0, a1 = 0;
     int bi = 0;
@@ -81,24 +73,14 @@ void plan_ere(const vp_eres2net_weights* w, int B, int T, void* ws, ErePlan& p) 
     p.total = c.off;
 }
 
-void conv_desc(vp_conv1d_desc& d, const vp_tdnn_layer& L, int dt) {
-    memset(&d, 0, sizeof(d));
-    vp_desc_dtype(d, dt); d.Cin = L.cin; d.Cout = L.cout; d.KW = L.kw; d.dilation = 1; d.stride = 1;
-    d.pad_mode = VP_PAD_ZERO; d.ldx = L.cin; d.ldy = L.cout;
-    vp_desc_weights(d, L);
-    d.bias = L.bias; d.bn_scale = L.bn_scale; d.bn_shift = L.bn_shift;
-}
-
-// x (B, t, f, .) -> 2-D conv geometry on d (3x3 pad 1 or 1x1, stride s on both axes)
-void geom2d(vp_conv1d_desc& d, int B, int t, int f, int s, bool k3) {
-    d.B = B; d.T_in = t; d.F_in = f; d.T_out = s == 2 ? down2(t) : t; d.F_out = s == 2 ? down2(f) : f;
-    d.KF = k3 ? 3 : 1; d.stride = s; d.stride_f = s; d.pad_left = k3 ? 1 : 0; d.pad_f = k3 ? 1 : 0;
-}
-
-// 1x1 convs over positions: the streaming kernel for the few-channel full-resolution stages (pointwise.hip), else the conv GEMM
-int conv1x1(vp_ctx* ctx, const vp_conv1d_desc& d, hipStream_t st) {
-    const int rc = vp_pointwise_bf16(ctx, &d, 1, st);
-    return rc == VP_EUNSUP ? vp_conv1d_fwd(ctx, &d, st) : rc;
+// a 1x1 conv with stride s on both axes of x (B, tin, fin, .): at s == 1 a pointwise conv over the P positions as one sequence
+int conv1x1_s(vp_ctx* ctx, vp_conv1d_desc& d, int B, int tin, int fin, int s, long long P, hipStream_t st) {
+    if (s == 1) {
+        vp_geom_rows(d, 1, (int)P, (int)P);
+        return vp_conv1x1(ctx, d, st);
+    }
+    vp_geom2d(d, B, tin, fin, s, false);
+    return vp_conv1d_fwd(ctx, &d, st);
 }
 
 // AFF (eres2net.py:33-53): out = x (1 + tanh(att)) + y (1 - tanh(att)), att = BN(conv(SiLU(BN(conv(cat(x, y))))))
@@ -110,11 +92,11 @@ int run_aff(vp_ctx* ctx, const vp_aff_weights& A, int dtc, const void* x, int ld
     if ((rc = vp_copy_cols(ctx, dt, y, ldy, yoff, cat, 2 * C, C, P, C, st))) return rc;
     if (P > 0x7fffffff / 4) VP_FAIL(ctx, VP_EINVAL, "aff: too many positions");
     vp_conv1d_desc d;
-    conv_desc(d, A.c1, dtc);
-    d.B = 1; d.T_in = (int)P; d.T_out = (int)P; d.x = cat; d.y = a1; d.act2 = VP_ACT_SILU;
+    vp_layer_desc(d, A.c1, dtc, VP_PAD_ZERO); vp_geom_rows(d, 1, (int)P, (int)P);
+    d.x = cat; d.y = a1; d.act2 = VP_ACT_SILU;
     if ((rc = vp_conv1d_fwd(ctx, &d, st))) return rc;
-    conv_desc(d, A.c2, dtc);
-    d.B = 1; d.T_in = (int)P; d.T_out = (int)P; d.x = a1; d.y = att; d.act2 = VP_ACT_TANH;
+    vp_layer_desc(d, A.c2, dtc, VP_PAD_ZERO); vp_geom_rows(d, 1, (int)P, (int)P);
+    d.x = a1; d.y = att; d.act2 = VP_ACT_TANH;
     if ((rc = vp_conv1d_fwd(ctx, &d, st))) return rc;
     return vp_aff_combine(ctx, dt, att, C, x, ldx, xoff, y, ldy, yoff, out, ldo, ooff, P, C, st);
 }
@@ -159,15 +141,12 @@ int vp_eres2net_fwd(vp_ctx* ctx, const vp_eres2net_weights* w, const void* feats
             if (b.scale < 1 || b.scale > VP_MAX_ERE_SCALE) VP_FAIL(ctx, VP_EINVAL, "eres2net: scale %d", b.scale);
             // o1 = hardtanh(bn1(conv1x1 stride s (x)))
             if (P > 0x7fffffff / 4) VP_FAIL(ctx, VP_EINVAL, "eres2net: too many positions");
-            conv_desc(d, b.conv1, dtc);
-            if (b.stride == 1) { d.B = 1; d.T_in = (int)P; d.T_out = (int)P; }
-            else geom2d(d, B, tin, fin, b.stride, false);
+            vp_layer_desc(d, b.conv1, dtc, VP_PAD_ZERO);
             d.x = x; d.y = p.o1; d.act2 = VP_ACT_HARDTANH20;
-            if ((rc = b.stride == 1 ? conv1x1(ctx, d, st) : vp_conv1d_fwd(ctx, &d, st))) return rc;
+            if ((rc = conv1x1_s(ctx, d, B, tin, fin, b.stride, P, st))) return rc;
             // chunk chain: sp_i = hardtanh(bn_i(conv3x3(in_i))) into o2[:, i*wd : (i+1)*wd]
             for (int i = 0; i < b.scale; ++i) {
-                conv_desc(d, b.convs[i], dtc);
-                geom2d(d, B, to, fo, 1, true);
+                vp_layer_desc(d, b.convs[i], dtc, VP_PAD_ZERO); vp_geom2d(d, B, to, fo, 1, true);
                 if (i == 0) { d.x = p.o1; d.ldx = W2; d.xoff = 0; }
                 else { d.x = p.spin; d.ldx = wd; d.xoff = 0; }
                 d.y = p.o2; d.ldy = W2; d.yoff = i * wd; d.act2 = VP_ACT_HARDTANH20;
@@ -186,19 +165,17 @@ int vp_eres2net_fwd(vp_ctx* ctx, const vp_eres2net_weights* w, const void* feats
             const void* res = x;
             int ld_res = b.conv1.cin;
             if (b.has_shortcut) {
-                conv_desc(d, b.shortcut, dtc);
-                if (b.stride == 1) { d.B = 1; d.T_in = (int)P; d.T_out = (int)P; }
-                else geom2d(d, B, tin, fin, b.stride, false);
+                vp_layer_desc(d, b.shortcut, dtc, VP_PAD_ZERO);
                 d.x = x; d.y = p.res;
-                if ((rc = b.stride == 1 ? conv1x1(ctx, d, st) : vp_conv1d_fwd(ctx, &d, st))) return rc;
+                if ((rc = conv1x1_s(ctx, d, B, tin, fin, b.stride, P, st))) return rc;
                 res = p.res; ld_res = Co;
             }
             // out = hardtanh(bn3(conv1x1(o2)) + residual); the last block of a stage lands in the stage buffer
             void* dst = j + 1 == w->stage_blocks[s] ? p.stage[s] : (x == p.xa ? p.xb : p.xa);
-            conv_desc(d, b.conv3, dtc);
-            d.B = 1; d.T_in = (int)P; d.T_out = (int)P; d.x = p.o2; d.y = dst;
+            vp_layer_desc(d, b.conv3, dtc, VP_PAD_ZERO); vp_geom_rows(d, 1, (int)P, (int)P);
+            d.x = p.o2; d.y = dst;
             d.res = res; d.ld_res = ld_res; d.act2 = VP_ACT_HARDTANH20;
-            if ((rc = conv1x1(ctx, d, st))) return rc;
+            if ((rc = vp_conv1x1(ctx, d, st))) return rc;
             x = dst;
         }
     }
@@ -210,8 +187,7 @@ int vp_eres2net_fwd(vp_ctx* ctx, const vp_eres2net_weights* w, const void* feats
     for (int k = w->first_fuse; k < 3; ++k) {
         const int C = w->down[k].cout;
         const long long P = (long long)B * p.t[k + 2] * p.f[k + 2];
-        conv_desc(d, w->down[k], dtc);
-        geom2d(d, B, p.t[k + 1], p.f[k + 1], 2, true);
+        vp_layer_desc(d, w->down[k], dtc, VP_PAD_ZERO); vp_geom2d(d, B, p.t[k + 1], p.f[k + 1], 2, true);
         d.x = low; d.y = p.ds;
         if ((rc = vp_conv1d_fwd(ctx, &d, st))) return rc;
         fout = (k & 1) ? p.fuse_b : p.fuse_a;

@@ -8,10 +8,11 @@
 // sp_{nums-1}]: the host permutes conv1's output channels and conv3's input channels to that order, so the pass-through chunk of a
 // 'normal' block is stored there by conv1's epilogue (y2 / ysplit) and the split convs write their column slices in place.  The
 // chain sp_{i+1} = sp_i + spx[i+1] comes from the conv epilogue's aux = y + add_in.  The final reshape is a permutation of the ASP /
-// Linear weights done at pack time (channel index f*C + c instead of c*F + f).
+// Linear weights done at pack time (channel index f*C + c instead of c*F + f).  Descriptors are built by launch.h (vp_layer_desc +
+// geometry); a call site sets only what is its own.
 #include <math.h>
 
-#include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -32,6 +33,7 @@ constexpr int STEM_LDS_MAX = 48 * 1024;
 
 int stem_out(int v) { return v >= 5 ? (v - 5) / 3 + 1 : 0; }     // conv 7, stride 3, pad 1
 int pool_out(int v) { return v >= 1 ? (v - 1) / 2 + 1 : 0; }     // pool 3, stride 2, pad 1 (also a 3x3 / 1x1 stride-2 conv)
+// (not launch.h's vp_down: this one maps an empty axis to 0, which the plan of a too-short input relies on; equal for v >= 1)
 int down(int v, int s) { return s == 2 ? pool_out(v) : v; }
 
 size_t stem_lds_bytes(int PT, int F, int CG, int Fc) {
@@ -310,19 +312,9 @@ int r2n_avgpool(vp_ctx* ctx, int dt, const void* x, int ldx, int xoff, void* y, 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // launch graph
 // ---------------------------------------------------------------------------------------------------------------------------------
-struct Carver {
-    char* base; size_t off;
-    explicit Carver(void* p) : base((char*)p), off(0) {}
-    void* take(size_t bytes) {
-        size_t o = off;
-        off += vp_align_up(bytes ? bytes : 1, 256);
-        return base ? (void*)(base + o) : nullptr;
-    }
-};
-
 struct R2nPlan {
-    void *xa, *xb, *o1, *cat, *aux[2], *res, *h;
-    float *e, *stats, *rowbias, *pooled;
+    void *xa, *xb, *o1, *cat, *aux[2], *res;
+    AspHeadBufs asp;
     size_t total;
     int Tp, Fp, T4, F4, C4;
 };
@@ -352,36 +344,13 @@ void plan_r2n(const vp_res2net_weights* w, int B, int T, void* ws, R2nPlan& p) {
     p.o1 = c.take(o1 * es); p.cat = c.take(cat * es);
     p.aux[0] = c.take(aux * es); p.aux[1] = c.take(aux * es);
     p.res = c.take(res * es);
-    p.h = c.take((size_t)B * t * w->asp.att * es);
-    p.e = (float*)c.take((size_t)B * t * Casp * 4);
-    p.stats = (float*)c.take((size_t)B * 2 * Casp * 4);
-    p.rowbias = (float*)c.take((size_t)B * w->asp.att * 4);
-    p.pooled = (float*)c.take((size_t)B * 2 * Casp * 4);
+    const AspHeadBytes ab = vp_asp_head_bytes(B, t, Casp, w->asp.att, es);
+    p.asp.h = c.take(ab.h);
+    p.asp.e = (float*)c.take(ab.e);
+    p.asp.stats = (float*)c.take(ab.stats);
+    p.asp.rowbias = (float*)c.take(ab.rowbias);
+    p.asp.pooled = (float*)c.take(ab.pooled);
     p.total = c.off;
-}
-
-void base_desc(vp_conv1d_desc& d, const vp_tdnn_layer& L, int dt) {
-    memset(&d, 0, sizeof(d));
-    vp_desc_dtype(d, dt); d.Cin = L.cin; d.Cout = L.cout; d.KW = L.kw; d.dilation = 1; d.stride = 1;
-    d.pad_mode = VP_PAD_ZERO; d.ldx = L.cin; d.ldy = L.cout;
-    vp_desc_weights(d, L);
-    d.bias = L.bias; d.bn_scale = L.bn_scale; d.bn_shift = L.bn_shift;
-}
-
-// 1x1 convs over positions: the streaming kernel for the few-channel full-resolution stages (pointwise.hip), else the conv GEMM
-int conv1x1(vp_ctx* ctx, const vp_conv1d_desc& d, hipStream_t st) {
-    const int rc = vp_pointwise_bf16(ctx, &d, 1, st);
-    return rc == VP_EUNSUP ? vp_conv1d_fwd(ctx, &d, st) : rc;
-}
-
-// a 1x1 conv with stride s on both axes (downsample): a plain pointwise conv over the positions when s == 1
-int conv1x1_strided(vp_ctx* ctx, vp_conv1d_desc& d, int B, int t, int f, int s, hipStream_t st) {
-    if (s == 1) {
-        d.B = B; d.T_in = t * f; d.T_out = t * f;
-        return conv1x1(ctx, d, st);
-    }
-    d.B = B; d.T_in = t; d.T_out = down(t, s); d.F_in = f; d.F_out = down(f, s); d.KF = 1; d.stride = s; d.stride_f = s;
-    return vp_conv1d_fwd(ctx, &d, st);
 }
 
 }  // namespace
@@ -473,17 +442,16 @@ int vp_res2net_fwd(vp_ctx* ctx, const vp_res2net_weights* w, const void* feats, 
         const int W = b.width, S = b.scale, Cc = W * S, nums = S > 1 ? S - 1 : 1;
         auto off = [&](int j) { return (S > 1 ? j + 1 : j) * W; };    // column of chunk j (sp_j) in the conv1 output and the concat
         // o1 = relu(bn1(conv1x1(x))); a normal block's pass-through chunk (column 0) also lands in the concat buffer
-        base_desc(d, b.conv1, dtc);
-        d.B = B; d.T_in = t * f; d.T_out = t * f; d.x = x; d.y = p.o1; d.act2 = VP_ACT_RELU;
+        vp_layer_desc(d, b.conv1, dtc, VP_PAD_ZERO); vp_geom_rows(d, B, t * f, t * f);
+        d.x = x; d.y = p.o1; d.act2 = VP_ACT_RELU;
         if (!b.stage && S > 1) { d.y2 = p.cat; d.ldy2 = Cc; d.y2off = 0; d.ysplit = W; }
-        if ((rc = conv1x1(ctx, d, st))) return rc;
+        if ((rc = vp_conv1x1(ctx, d, st))) return rc;
         // sp_j = relu(bn(conv3x3 stride s (spx[j] | sp_{j-1} + spx[j]))) into the concat's column slice; a normal block's conv j also
         // writes the next conv's input sp_j + spx[j+1] (aux)
         for (int j = 0; j < nums; ++j) {
             const bool chained = !b.stage && j > 0;
-            base_desc(d, b.convs[j], dtc);
-            d.B = B; d.T_in = t; d.T_out = to; d.F_in = f; d.F_out = fo; d.KF = 3; d.stride = b.stride; d.stride_f = b.stride;
-            d.pad_left = 1; d.pad_f = 1; d.act2 = VP_ACT_RELU;
+            vp_layer_desc(d, b.convs[j], dtc, VP_PAD_ZERO); vp_geom2d(d, B, t, f, b.stride, true);
+            d.act2 = VP_ACT_RELU;
             d.x = chained ? p.aux[(j - 1) & 1] : p.o1; d.ldx = chained ? W : Cc; d.xoff = chained ? 0 : off(j);
             d.y = p.cat; d.ldy = Cc; d.yoff = off(j);
             if (!b.stage && j + 1 < nums) {
@@ -497,27 +465,23 @@ int vp_res2net_fwd(vp_ctx* ctx, const vp_res2net_weights* w, const void* feats, 
         const void* res = x;
         int ldr = b.conv1.cin;
         if (b.has_down) {          // bn(conv1x1 stride (s, s)(x))
-            base_desc(d, b.down, dtc);
+            vp_layer_desc(d, b.down, dtc, VP_PAD_ZERO);
             d.x = x; d.y = p.res;
-            if ((rc = conv1x1_strided(ctx, d, B, t, f, b.stride, st))) return rc;
+            if ((rc = vp_conv1x1_strided(ctx, d, B, t, f, b.stride, st))) return rc;
             res = p.res; ldr = b.down.cout;
         }
         // x <- relu(bn3(conv1x1(concat)) + residual)
-        base_desc(d, b.conv3, dtc);
-        d.B = B; d.T_in = to * fo; d.T_out = to * fo; d.x = p.cat; d.y = xn; d.res = res; d.ld_res = ldr; d.res_off = 0;
+        vp_layer_desc(d, b.conv3, dtc, VP_PAD_ZERO); vp_geom_rows(d, B, to * fo, to * fo);
+        d.x = p.cat; d.y = xn; d.res = res; d.ld_res = ldr; d.res_off = 0;
         d.act2 = VP_ACT_RELU;
-        if ((rc = conv1x1(ctx, d, st))) return rc;
+        if ((rc = vp_conv1x1(ctx, d, st))) return rc;
         void* tmp = x; x = xn; xn = tmp;
         t = to; f = fo;
     }
     // ASP over time on (B, T4, F4*C4), then bn2 -> linear -> bn3 (folded + permuted at pack time)
     const int Casp = p.F4 * p.C4;
     if (w->asp.C != Casp) VP_FAIL(ctx, VP_EINVAL, "res2net: asp.C %d != %d (F' %d x C %d)", w->asp.C, Casp, p.F4, p.C4);
-    if ((rc = vp_time_moments(ctx, dt, x, Casp, B, t, Casp, 1e-12f, 0, p.stats, st))) return rc;
-    VpAspBufs ab{p.h, p.e, nullptr, nullptr, p.stats, p.rowbias, p.pooled};
-    if ((rc = vp_run_asp(ctx, w->asp, dtc, x, Casp, nullptr, B, t, ab, st))) return rc;
-    return vp_dense_f32_ex(ctx, p.pooled, 2 * Casp, w->lin_w, 0, w->lin_b, nullptr, nullptr, B, w->embd_dim, 2 * Casp,
-                           VP_ACT_NONE, emb, w->embd_dim, st);
+    return vp_asp_head(ctx, w->asp, dtc, x, B, t, Casp, p.asp, w->lin_w, w->lin_b, w->embd_dim, emb, st);
 }
 
 }  // extern "C"

@@ -7,28 +7,18 @@
 // average falls out of conv3's fused column sums), the 3x3 / strided 1x1 convs use the conv GEMM's 2-D
 // loader, SE gate + residual + ReLU is one elementwise pass, and the final reshape is a permutation of
 // the ASP / Linear weights done at pack time (channel index f*C + c instead of c*F + f).
-#include "common.h"
+// Descriptors are built by launch.h (vp_layer_desc + geometry); a call site sets only what is its own.
+#include "launch.h"
 
 namespace {
 
-struct Carver {
-    char* base; size_t off;
-    explicit Carver(void* p) : base((char*)p), off(0) {}
-    void* take(size_t bytes) {
-        size_t o = off;
-        off += vp_align_up(bytes ? bytes : 1, 256);
-        return base ? (void*)(base + o) : nullptr;
-    }
-};
-
 struct RsePlan {
-    void *xa, *xb, *o1, *o2, *o3, *res, *h;
-    float *e, *psum, *stats, *se_h, *se_s, *rowbias, *pooled;
+    void *xa, *xb, *o1, *o2, *o3, *res;
+    float *psum, *se_h, *se_s;
+    AspHeadBufs asp;
     size_t total;
     int T4, F4, C4;
 };
-
-int down(int v, int s) { return s == 2 ? (v - 1) / 2 + 1 : v; }
 
 void plan_rse(const vp_resnetse_weights* w, int B, int T, void* ws, RsePlan& p) {
     const size_t es = vp_dtype_size(w->dtype);
@@ -38,7 +28,7 @@ void plan_rse(const vp_resnetse_weights* w, int B, int T, void* ws, RsePlan& p) 
     for (int i = 0; i < w->n_blocks; ++i) {
         const vp_rse_block& b = w->blk[i];
         const size_t pin = (size_t)B * t * f;
-        const int to = down(t, b.stride), fo = down(f, b.stride);
+        const int to = vp_down(t, b.stride), fo = vp_down(f, b.stride);
         const size_t pout = (size_t)B * to * fo;
         if (pin * b.conv1.cout > small) small = pin * b.conv1.cout;
         if (pout * b.conv3.cout > big) big = pout * b.conv3.cout;
@@ -50,32 +40,20 @@ void plan_rse(const vp_resnetse_weights* w, int B, int T, void* ws, RsePlan& p) 
     }
     p.T4 = t; p.F4 = f; p.C4 = w->blk[w->n_blocks - 1].conv3.cout;
     const int Casp = p.F4 * p.C4;
+    const AspHeadBytes ab = vp_asp_head_bytes(B, t, Casp, w->asp.att, es);
+    const size_t stats_se = (size_t)B * 2 * cmax * 4;        // the statistics buffer is sized for the widest block as well
     Carver c(ws);
     p.xa = c.take(big * es); p.xb = c.take(big * es); p.o3 = c.take(big * es); p.res = c.take(big * es);
     p.o1 = c.take(small * es); p.o2 = c.take(small * es);
-    p.h = c.take((size_t)B * t * w->asp.att * es);
-    p.e = (float*)c.take((size_t)B * t * Casp * 4);
+    p.asp.h = c.take(ab.h);
+    p.asp.e = (float*)c.take(ab.e);
     p.psum = (float*)c.take(ps);
-    p.stats = (float*)c.take((size_t)B * 2 * (Casp > cmax ? Casp : cmax) * 4);
+    p.asp.stats = (float*)c.take(ab.stats > stats_se ? ab.stats : stats_se);
     p.se_h = (float*)c.take((size_t)B * cmax * 4);
     p.se_s = (float*)c.take((size_t)B * cmax * 4);
-    p.rowbias = (float*)c.take((size_t)B * w->asp.att * 4);
-    p.pooled = (float*)c.take((size_t)B * 2 * Casp * 4);
+    p.asp.rowbias = (float*)c.take(ab.rowbias);
+    p.asp.pooled = (float*)c.take(ab.pooled);
     p.total = c.off;
-}
-
-void base_desc(vp_conv1d_desc& d, const vp_tdnn_layer& L, int dt) {
-    memset(&d, 0, sizeof(d));
-    vp_desc_dtype(d, dt); d.Cin = L.cin; d.Cout = L.cout; d.KW = L.kw; d.dilation = 1; d.stride = 1;
-    d.pad_mode = VP_PAD_ZERO; d.ldx = L.cin; d.ldy = L.cout;
-    vp_desc_weights(d, L);
-    d.bias = L.bias; d.bn_scale = L.bn_scale; d.bn_shift = L.bn_shift;
-}
-
-// 1x1 convs over positions: the streaming kernel for the few-channel full-resolution stages (pointwise.hip), else the conv GEMM
-int conv1x1(vp_ctx* ctx, const vp_conv1d_desc& d, hipStream_t st) {
-    const int rc = vp_pointwise_bf16(ctx, &d, 1, st);
-    return rc == VP_EUNSUP ? vp_conv1d_fwd(ctx, &d, st) : rc;
 }
 
 }  // namespace
@@ -118,12 +96,12 @@ int vp_resnetse_fwd(vp_ctx* ctx, const vp_resnetse_weights* w, const void* feats
     int t = T, f = w->feat_dim;
     for (int i = 0; i < w->n_blocks; ++i) {
         const vp_rse_block& b = w->blk[i];
-        const int to = down(t, b.stride), fo = down(f, b.stride);
+        const int to = vp_down(t, b.stride), fo = vp_down(f, b.stride);
         const int C = b.conv3.cout;
         // o1 = relu(bn1(conv1x1(x))): a GEMM over the B*t*f positions
-        base_desc(d, b.conv1, dtc);
-        d.B = B; d.T_in = t * f; d.T_out = t * f; d.x = x; d.y = p.o1; d.act2 = VP_ACT_RELU;
-        if ((rc = conv1x1(ctx, d, st))) return rc;
+        vp_layer_desc(d, b.conv1, dtc, VP_PAD_ZERO); vp_geom_rows(d, B, t * f, t * f);
+        d.x = x; d.y = p.o1; d.act2 = VP_ACT_RELU;
+        if ((rc = vp_conv1x1(ctx, d, st))) return rc;
         // o2 = relu(bn2(conv3x3 stride s (o1))): the stage-1 blocks (32 -> 32 channels, stride 1, full-resolution maps) run on the
         // slab kernel of the CAM++ FCM head (fcm_conv.hip), the rest on the conv GEMM's 2-D loader
         int fast = VP_EUNSUP;
@@ -131,26 +109,21 @@ int vp_resnetse_fwd(vp_ctx* ctx, const vp_resnetse_weights* w, const void* feats
             fast = vp_conv3x3_c32_bf16(ctx, p.o1, p.o2, &b.conv2, nullptr, 1, nullptr, nullptr, B, t, f, 1, nullptr, nullptr, nullptr, nullptr, nullptr, st);
         if (fast != VP_OK && fast != VP_EUNSUP) return fast;
         if (fast != VP_OK) {
-            base_desc(d, b.conv2, dtc);
-            d.B = B; d.T_in = t; d.T_out = to; d.F_in = f; d.F_out = fo; d.KF = 3; d.stride = b.stride; d.stride_f = b.stride;
-            d.pad_left = 1; d.pad_f = 1; d.x = p.o1; d.y = p.o2; d.act2 = VP_ACT_RELU;
+            vp_layer_desc(d, b.conv2, dtc, VP_PAD_ZERO); vp_geom2d(d, B, t, f, b.stride, true);
+            d.x = p.o1; d.y = p.o2; d.act2 = VP_ACT_RELU;
             if ((rc = vp_conv1d_fwd(ctx, &d, st))) return rc;
         }
         // o3 = bn3(conv1x1(o2)) with the per-utterance sums of the SE squeeze fused in
-        base_desc(d, b.conv3, dtc);
-        d.B = B; d.T_in = to * fo; d.T_out = to * fo; d.x = p.o2; d.y = p.o3; d.psum = p.psum;
-        if ((rc = conv1x1(ctx, d, st))) return rc;
+        vp_layer_desc(d, b.conv3, dtc, VP_PAD_ZERO); vp_geom_rows(d, B, to * fo, to * fo);
+        d.x = p.o2; d.y = p.o3; d.psum = p.psum;
+        if ((rc = vp_conv1x1(ctx, d, st))) return rc;
         if ((rc = vp_se_gate(ctx, p.psum, b.conv3.bn_shift, B, to * fo, C, C / 8, b.se_w1, b.se_b1, b.se_w2, b.se_b2, p.se_s, st)))
             return rc;
         const void* res = x;
         if (b.has_down) {          // bn(conv1x1 stride (s, s)(x))
-            base_desc(d, b.down, dtc);
-            d.B = B; d.T_in = t; d.T_out = to; d.F_in = f; d.F_out = fo; d.KF = 1; d.stride = b.stride; d.stride_f = b.stride;
+            vp_layer_desc(d, b.down, dtc, VP_PAD_ZERO);
             d.x = x; d.y = p.res;
-            if (b.stride == 1) {           // a plain pointwise conv over the B * t * f positions
-                d.T_in = t * f; d.T_out = t * f; d.F_in = 0; d.F_out = 0; d.KF = 0; d.stride = 1; d.stride_f = 0;
-                if ((rc = conv1x1(ctx, d, st))) return rc;
-            } else if ((rc = vp_conv1d_fwd(ctx, &d, st))) return rc;
+            if ((rc = vp_conv1x1_strided(ctx, d, B, t, f, b.stride, st))) return rc;
             res = p.res;
         }
         // x <- relu(o3 * s + residual)
@@ -161,11 +134,7 @@ int vp_resnetse_fwd(vp_ctx* ctx, const vp_resnetse_weights* w, const void* feats
     // ASP over time on (B, T4, F4*C4), then bn2 -> linear -> bn3 (folded + permuted at pack time)
     const int Casp = p.F4 * p.C4;
     if (w->asp.C != Casp) VP_FAIL(ctx, VP_EINVAL, "resnetse: asp.C %d != %d", w->asp.C, Casp);
-    if ((rc = vp_time_moments(ctx, dt, x, Casp, B, t, Casp, 1e-12f, 0, p.stats, st))) return rc;
-    VpAspBufs ab{p.h, p.e, nullptr, nullptr, p.stats, p.rowbias, p.pooled};
-    if ((rc = vp_run_asp(ctx, w->asp, dtc, x, Casp, nullptr, B, t, ab, st))) return rc;
-    return vp_dense_f32_ex(ctx, p.pooled, 2 * Casp, w->lin_w, 0, w->lin_b, nullptr, nullptr, B, w->embd_dim, 2 * Casp,
-                           VP_ACT_NONE, emb, w->embd_dim, st);
+    return vp_asp_head(ctx, w->asp, dtc, x, B, t, Casp, p.asp, w->lin_w, w->lin_b, w->embd_dim, emb, st);
 }
 
 }  // extern "C"

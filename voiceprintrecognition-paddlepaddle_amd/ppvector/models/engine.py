@@ -18,6 +18,11 @@ from ppvector.models.utils import f32, pack_conv_weight, pack_hl32
 _TORCH_DT = {'float32': torch.float32, 'float32x3': torch.float32, 'bfloat16': torch.bfloat16}
 
 
+def _w1x1_t(conv):
+    """Weight of a 1x1 Conv1D as f32 [in][out] (input-major): the SE and context-gate kernels read it that way."""
+    return conv.weight.detach()[:, :, 0].float().t().contiguous()
+
+
 def _versions(module):
     """Cache key of a packed engine: torch's version counters (in-place torch writes, load_state_dict) plus the epoch of
     raw-pointer writers (Adam step, train-mode BatchNorm statistics), which the counters do not see."""
@@ -25,6 +30,8 @@ def _versions(module):
 
 
 class _Engine:
+    _ws_fn = _fwd_fn = None       # names of the backbone's vp_X_workspace_bytes / vp_X_fwd entry points (include/vpmi.h)
+
     def __init__(self, module, dtype_name):
         self.dtype_name = dtype_name
         self.tdtype = _TORCH_DT[dtype_name]
@@ -43,17 +50,20 @@ class _Engine:
         self.keep.append(t)
         return t.data_ptr()
 
-    def tdnn_layer(self, L, conv, bn, dil, w_override=None):
-        """conv: _ConvParams; bn: _BNParams or None."""
-        cout, cin, kw = conv.weight.shape
-        w = w_override if w_override is not None else pack_conv_weight(conv.weight, self.tdtype)
-        L.w = self._p(w)
+    def conv_layer(self, L, conv, bn, kw_taps, w_packed, dil=1):
+        """Fill a vp_tdnn_layer from packed weights [cout][kw_taps * cin]; conv gives the bias, bn (or None) the folded affine."""
+        L.w = self._p(w_packed)
+        self.split_weights(L, w_packed)
         L.bias = self._p(f32(conv.bias))
         if bn is not None:
             sc, sh = bn.folded()
             L.bn_scale, L.bn_shift = self._p(sc), self._p(sh)
-        L.cin, L.cout, L.kw, L.dil = (w.shape[1] // kw), cout, kw, dil
-        self.split_weights(L, w)
+        L.cin, L.cout, L.kw, L.dil = w_packed.shape[1] // kw_taps, w_packed.shape[0], kw_taps, dil
+
+    def tdnn_layer(self, L, conv, bn, dil, w_override=None):
+        """conv: _ConvParams (Conv1D, weight (cout, cin, kw)); bn: _BNParams or None."""
+        w = w_override if w_override is not None else pack_conv_weight(conv.weight, self.tdtype)
+        self.conv_layer(L, conv, bn, conv.weight.shape[2], w, dil)
 
     def split_weights(self, L, w):
         """'float32x3': the same [cout][K] weights as split bf16 planes, K zero-padded to a multiple of 32 (vp_tdnn_layer.w_hl) -- the conv
@@ -109,6 +119,14 @@ class _Engine:
             cur.wait_stream(self._streams[i])      # everything allocated above is reused only behind this join
         return emb
 
+    def _launch(self, xin, emb, slot=0):
+        B, T, F = xin.shape
+        lib, ctx = N.lib(), N.ctx(xin.device)
+        nws = getattr(lib, self._ws_fn)(C.byref(self.W), B, T)
+        ws = self.workspace(nws, xin.device, slot)
+        N.check(getattr(lib, self._fwd_fn)(ctx, C.byref(self.W), xin.data_ptr(), B, T, emb.data_ptr(), ws.data_ptr(),
+                                           ws.numel(), N.stream_ptr()), ctx)
+
     def forward(self, x):
         xin = self.feats_in(x)
         emb = torch.empty((xin.shape[0], self.W.embd_dim), dtype=torch.float32, device=xin.device)
@@ -134,6 +152,8 @@ class _Engine:
 
 
 class EcapaEngine(_Engine):
+    _ws_fn, _fwd_fn = 'vp_ecapa_workspace_bytes', 'vp_ecapa_fwd'
+
     def __init__(self, m, dtype_name):
         super().__init__(m, dtype_name)
         W = N.EcapaWeights()
@@ -149,9 +169,9 @@ class EcapaEngine(_Engine):
             for j, rb in enumerate(blk.res2net_block.blocks):
                 self.tdnn_layer(S.res2[j], rb.conv.conv, rb.norm.norm, rb.conv.dilation)
             self.tdnn_layer(S.tdnn2, blk.tdnn2.conv.conv, blk.tdnn2.norm.norm, 1)
-            S.se_w1 = self._p(blk.se_block.conv1.conv.weight.detach()[:, :, 0].float().t().contiguous())     # [C][se_ch]
+            S.se_w1 = self._p(_w1x1_t(blk.se_block.conv1.conv))     # [C][se_ch]
             S.se_b1 = self._p(f32(blk.se_block.conv1.conv.bias))
-            S.se_w2 = self._p(blk.se_block.conv2.conv.weight.detach()[:, :, 0].float().t().contiguous())     # [se_ch][C]
+            S.se_w2 = self._p(_w1x1_t(blk.se_block.conv2.conv))     # [se_ch][C]
             S.se_b2 = self._p(f32(blk.se_block.conv2.conv.bias))
         self.tdnn_layer(W.mfa, m.mfa.conv.conv, m.mfa.norm.norm, m.mfa.conv.dilation)
         self.asp(W.asp, m.asp)
@@ -167,16 +187,10 @@ class EcapaEngine(_Engine):
         ecapa_hl_ok), False on the generic split-precision path and on the other engines.  Host only: needs no GPU."""
         return bool(N.lib().vp_ecapa_x3_fast_path(C.byref(self.W), int(B), int(T)))
 
-    def _launch(self, xin, emb, slot=0):
-        B, T, F = xin.shape
-        lib, ctx = N.lib(), N.ctx(xin.device)
-        nws = lib.vp_ecapa_workspace_bytes(C.byref(self.W), B, T)
-        ws = self.workspace(nws, xin.device, slot)
-        N.check(lib.vp_ecapa_fwd(ctx, C.byref(self.W), xin.data_ptr(), B, T, emb.data_ptr(), ws.data_ptr(),
-                       ws.numel(), N.stream_ptr()), ctx)
-
 
 class TdnnEngine(_Engine):
+    _ws_fn, _fwd_fn = 'vp_tdnn_workspace_bytes', 'vp_tdnn_fwd'
+
     def __init__(self, m, dtype_name):
         super().__init__(m, dtype_name)
         W = N.TdnnWeights()
@@ -195,26 +209,10 @@ class TdnnEngine(_Engine):
         W.lin_b = self._p((lb + lw @ h5) * s6 + h6)
         self.W = W
 
-    def _launch(self, xin, emb, slot=0):
-        B, T, F = xin.shape
-        lib, ctx = N.lib(), N.ctx(xin.device)
-        nws = lib.vp_tdnn_workspace_bytes(C.byref(self.W), B, T)
-        ws = self.workspace(nws, xin.device, slot)
-        N.check(lib.vp_tdnn_fwd(ctx, C.byref(self.W), xin.data_ptr(), B, T, emb.data_ptr(), ws.data_ptr(),
-                       ws.numel(), N.stream_ptr()), ctx)
-
 
 class CamppEngine(_Engine):
     """Packs a CAMPPlus module into vp_campplus_weights (include/vpmi.h)."""
-
-    def conv_layer(self, L, conv, bn, kw_taps, w_packed, dil=1):
-        L.w = self._p(w_packed)
-        self.split_weights(L, w_packed)
-        L.bias = self._p(f32(conv.bias))
-        if bn is not None:
-            sc, sh = bn.folded()
-            L.bn_scale, L.bn_shift = self._p(sc), self._p(sh)
-        L.cin, L.cout, L.kw, L.dil = w_packed.shape[1] // kw_taps, w_packed.shape[0], kw_taps, dil
+    _ws_fn, _fwd_fn = 'vp_campplus_workspace_bytes', 'vp_campplus_fwd'
 
     def conv2d(self, L, conv, bn):
         w = conv.weight.detach()                                  # (Cout, Cin, kF, kT)
@@ -264,9 +262,9 @@ class CamppEngine(_Engine):
                                 lay.linear1.weight.detach()[:, :, 0].to(self.tdtype).contiguous())
                 cl = lay.cam_layer
                 self.conv_layer(L.local, cl.linear_local, None, k, pack_conv_weight(cl.linear_local.weight, self.tdtype), d)
-                L.ctx_w1 = self._p(cl.linear1.weight.detach()[:, :, 0].float().t().contiguous())        # [in][out]
+                L.ctx_w1 = self._p(_w1x1_t(cl.linear1))
                 L.ctx_b1 = self._p(f32(cl.linear1.bias))
-                L.ctx_w2 = self._p(cl.linear2.weight.detach()[:, :, 0].float().t().contiguous())
+                L.ctx_w2 = self._p(_w1x1_t(cl.linear2))
                 L.ctx_b2 = self._p(f32(cl.linear2.bias))
                 li += 1
             tr = getattr(xv, f'transit{bi}')
@@ -281,14 +279,6 @@ class CamppEngine(_Engine):
         W.dense_w = self._p(dw * ds[:, None])
         W.dense_b = self._p(xv.dense.linear.bias.detach().float() * ds + dh)
         self.W = W
-
-    def _launch(self, xin, emb, slot=0):
-        B, T, F = xin.shape
-        lib, ctx = N.lib(), N.ctx(xin.device)
-        nws = lib.vp_campplus_workspace_bytes(C.byref(self.W), B, T)
-        ws = self.workspace(nws, xin.device, slot)
-        N.check(lib.vp_campplus_fwd(ctx, C.byref(self.W), xin.data_ptr(), B, T, emb.data_ptr(), ws.data_ptr(),
-                       ws.numel(), N.stream_ptr()), ctx)
 
 
 def _pack_permuted_asp_head(eng, W, m, C4, Fq):
@@ -322,6 +312,7 @@ def _pack_permuted_asp_head(eng, W, m, C4, Fq):
 
 class ResNetSEEngine(CamppEngine):
     """Packs a ResNetSE module into vp_resnetse_weights (include/vpmi.h)."""
+    _ws_fn, _fwd_fn = 'vp_resnetse_workspace_bytes', 'vp_resnetse_fwd'
 
     def __init__(self, m, dtype_name):
         _Engine.__init__(self, m, dtype_name)
@@ -353,14 +344,6 @@ class ResNetSEEngine(CamppEngine):
         _pack_permuted_asp_head(self, W, m, blocks[-1].conv3.weight.shape[0], m.input_size // 8)
         self.W = W
 
-    def _launch(self, xin, emb, slot=0):
-        B, T, F = xin.shape
-        lib, ctx = N.lib(), N.ctx(xin.device)
-        nws = lib.vp_resnetse_workspace_bytes(C.byref(self.W), B, T)
-        ws = self.workspace(nws, xin.device, slot)
-        N.check(lib.vp_resnetse_fwd(ctx, C.byref(self.W), xin.data_ptr(), B, T, emb.data_ptr(), ws.data_ptr(),
-                       ws.numel(), N.stream_ptr()), ctx)
-
 
 def _ceil8(v):
     return (v + 7) // 8 * 8
@@ -375,6 +358,7 @@ class Eres2netEngine(CamppEngine):
     """Packs an ERes2Net / ERes2NetV2 module into vp_eres2net_weights (include/vpmi.h).  Chunk widths that are not multiples
     of 8 (V2: 13 / 26 / 52 / 104) are zero-padded: padded channels carry zero weights, zero bias and a zero BN affine, so they
     stay exactly 0 through Hardtanh / SiLU / tanh and the AFF combine, and meet zero weight columns downstream."""
+    _ws_fn, _fwd_fn = 'vp_eres2net_workspace_bytes', 'vp_eres2net_fwd'
 
     def conv2d_pad(self, L, conv, bn, in_map=None, cin_p=None, out_map=None, cout_p=None):
         w = conv.weight.detach().float()                            # (Cout, Cin, kF, kT)
@@ -466,19 +450,12 @@ class Eres2netEngine(CamppEngine):
         W.seg_b = self._p(f32(m.seg_1.bias))
         self.W = W
 
-    def _launch(self, xin, emb, slot=0):
-        B, T, F = xin.shape
-        lib, ctx = N.lib(), N.ctx(xin.device)
-        nws = lib.vp_eres2net_workspace_bytes(C.byref(self.W), B, T)
-        ws = self.workspace(nws, xin.device, slot)
-        N.check(lib.vp_eres2net_fwd(ctx, C.byref(self.W), xin.data_ptr(), B, T, emb.data_ptr(), ws.data_ptr(),
-                       ws.numel(), N.stream_ptr()), ctx)
-
 
 class Res2NetEngine(Eres2netEngine):
     """Packs a Res2Net module into vp_res2net_weights (include/vpmi.h).  The concat of a Bottle2neck is kept as [last chunk | sp_0 |
     ... | sp_{nums-1}]: conv1's output channels and conv3's input channels are permuted to that order (the pass-through chunk then
     comes out of conv1's epilogue, csrc/res2net.hip).  Chunk widths that are not multiples of 8 are zero-padded as in ERes2Net."""
+    _ws_fn, _fwd_fn = 'vp_res2net_workspace_bytes', 'vp_res2net_fwd'
 
     def __init__(self, m, dtype_name):
         _Engine.__init__(self, m, dtype_name)
@@ -512,14 +489,6 @@ class Res2NetEngine(Eres2netEngine):
         from ppvector.models.res2net import feature_bins
         _pack_permuted_asp_head(self, W, m, blocks[-1].conv3.weight.shape[0], feature_bins(m.input_size))
         self.W = W
-
-    def _launch(self, xin, emb, slot=0):
-        B, T, F = xin.shape
-        lib, ctx = N.lib(), N.ctx(xin.device)
-        nws = lib.vp_res2net_workspace_bytes(C.byref(self.W), B, T)
-        ws = self.workspace(nws, xin.device, slot)
-        N.check(lib.vp_res2net_fwd(ctx, C.byref(self.W), xin.data_ptr(), B, T, emb.data_ptr(), ws.data_ptr(),
-                       ws.numel(), N.stream_ptr()), ctx)
 
 
 def _graph_forward(eng, x):
