@@ -957,6 +957,31 @@ size_t vp_cosine_scores_workspace_bytes(int Na, int Nb, int D);
 int vp_cosine_scores_f32(vp_ctx* ctx, const float* a, const float* b, int Na, int Nb, int D, float* scores,
                          void* ws, size_t ws_bytes, vp_stream stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Speaker diarization around the embedding forward (csrc/diarize.hip).  All f32 whatever the compute dtype of the backbones:
+ * the pruning is a selection, a narrower format would change which entries survive.  No float atomics: two runs give the same bits.
+ * vp_chunk_batch_f32 -- the fixed-length windows of ONE recording as a batch; replaces the per-chunk np.pad of
+ *   SpeakerDiarization._chunk (infer_utils/speaker_diarization.py:75-77) and the per-chunk _load_audio normalisation + separate
+ *   upload of predict_batch (predict.py:213-215, :242-260).  table: DEVICE [N][2] = (first sample, one past the last) into wave
+ *   (clamped to [0, wave_len]; at most chunk_len samples are taken).  out[b] (N, chunk_len) = the window zero-padded on the right,
+ *   then, if normalize, scaled by 10^(g / 20), g = min(target_db - 10 log10(max(mean x^2, 1e-20)), 300), the mean taken over the
+ *   PADDED row (the reference pads before it normalises).  Mean square and gain are carried in f64.  One workgroup per row.
+ * vp_affinity_prune_f32 -- replaces SpectralCluster.get_sim_mat + p_pruning (:253-273): P[i][j] = cos(x_i, x_j) with the n_elems
+ *   smallest entries of row i set to 0 (n_elems is the host's int((1 - pval) * N), :261-265).  The unpruned matrix is never
+ *   written: a row block's similarities stay in LDS, where the row's n_elems-th smallest value is found by a radix selection.
+ *   Equal values at the threshold: the ones in the LOWER columns are zeroed first (the reference's argsort leaves this undefined).
+ *   2 <= N <= 16384, 1 <= D <= 1024, 0 <= n_elems < N, else VP_EINVAL.  A zero embedding has cosine 0 with everything.
+ * vp_laplacian_f32 -- replaces the symmetrisation at :246 and get_laplacian (:276-282): M = (P + P^T) / 2 with a zero diagonal,
+ *   L = diag(sum_j |M_ij|) - M.  L is exactly symmetric.  Out of place (L == P is VP_EINVAL): a workgroup reads tiles of P that
+ *   another one's output would already have replaced.  1 <= N <= 16384.
+ * ---------------------------------------------------------------------------------------------- */
+int vp_chunk_batch_f32(vp_ctx* ctx, const float* wave, int wave_len, const int32_t* table, int N, int chunk_len, int normalize,
+                       float target_db, float* out, vp_stream stream);
+size_t vp_affinity_prune_workspace_bytes(int N, int D);
+int vp_affinity_prune_f32(vp_ctx* ctx, const float* emb, int N, int D, int n_elems, float* P, void* ws, size_t ws_bytes,
+                          vp_stream stream);
+int vp_laplacian_f32(vp_ctx* ctx, const float* P, int N, float* L, vp_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -389,6 +389,10 @@ _PROTOS = {
     'vp_cosine_scores_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'vp_cosine_scores_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                      c_size_t, c_void_p]),
+    'vp_chunk_batch_f32': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
+    'vp_affinity_prune_workspace_bytes': (c_size_t, [c_int, c_int]),
+    'vp_affinity_prune_f32': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'vp_laplacian_f32': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS.keys())

@@ -5,7 +5,10 @@ mask, one featurizer call, backbone in chunks), ``contrast`` (:271-283) and the 
 (:173-187, :337-342) -- Fbank+CMN, backbone forward and cosine scoring all go through libvpmi.
 Host bookkeeping kept in Python as in the reference: audio decoding / resampling / dB normalisation
 (``_load_audio`` :189-216, yeaudio semantics restated for PCM WAV + ndarray input), the user index
-(pickle ``audio_indexes.bin`` with the reference's key names, :86-109).  Speaker diarisation is out of scope.
+(pickle ``audio_indexes.bin`` with the reference's key names, :86-109).
+``speaker_diarization`` (:366-396): the windows are cut, padded and normalised on the GPU from one upload of the recording, embedded
+by the same featurizer + backbone, and clustered through the pruned-affinity and Laplacian kernels (``ppvector/infer_utils``); the
+voice-activity detection in front of it is not built -- the caller passes the speech regions.
 """
 import io
 import os
@@ -20,6 +23,7 @@ import yaml
 from torch import nn
 
 from ppvector.data_utils.featurizer import AudioFeaturizer
+from ppvector.infer_utils.speaker_diarization import SpeakerDiarization, chunk_batch
 from ppvector.metric.metrics import cosine_score_matrix
 from ppvector.models import build_model
 from ppvector.utils.utils import dict_to_object
@@ -114,6 +118,7 @@ class PPVectorPredictor:
         self.audio_feature = None
         self.users_name, self.users_audio_path = [], []
         self.audio_db_path = audio_db_path
+        self.speaker_diarize = SpeakerDiarization()
         if self.audio_db_path is not None:
             self.audio_indexes_path = os.path.join(audio_db_path, "audio_indexes.bin")
             self.__load_audio_db(self.audio_db_path)
@@ -250,6 +255,48 @@ class PPVectorPredictor:
 
     def get_users(self):
         return self.users_name
+
+    # ------------------------------------------------------------------ diarization
+    def chunk_embeddings(self, audio_segment, table, batch_size=32):
+        """Embeddings (N, embd_dim) of the windows ``table`` (rows ``[start_s, end_s, first_sample, end_sample]``) of a loaded
+        recording: one upload, the windows cut / zero-padded / dB-normalised by vp_chunk_batch_f32 as ``_load_audio`` would do to each
+        of them, then the featurizer (all rows have one length: no ratio mask) and the backbone in slices of ``batch_size``."""
+        ds = self.configs.dataset_conf.dataset
+        wave = torch.from_numpy(np.ascontiguousarray(audio_segment.samples, dtype=np.float32)).to(self.device)
+        offsets = np.asarray([[row[2], row[3]] for row in table], dtype=np.int32)
+        chunks = chunk_batch(wave, offsets, self.speaker_diarize.chunk_len, normalize=bool(ds.use_dB_normalization),
+                             target_db=float(ds.target_dB))
+        outs = []
+        for i in range(0, chunks.shape[0], batch_size):
+            feat = self._audio_featurizer(chunks[i:i + batch_size])
+            outs.append(self.predictor(feat).cpu().numpy())
+        return np.concatenate(outs, axis=0)
+
+    def speaker_diarization(self, audio_data, sample_rate=16000, speaker_num=None, search_audio_db=False, vad_segments=None):
+        """说话人日志识别 -> [dict(speaker, start, end)] (predict.py:366-396).
+
+        ``vad_segments``: the speech regions as (start_s, end_s) pairs, the one argument the reference does not have.  Its own
+        regions come from yeaudio's model-based ``AudioSegment.vad``, which is not built here; without ``vad_segments`` the call raises.
+        """
+        if vad_segments is None:
+            raise NotImplementedError('voice-activity detection (yeaudio AudioSegment.vad) is not built on the HIP engine: '
+                                      'pass the speech regions as vad_segments=[(start_s, end_s), ...]')
+        seg = self._load_audio(audio_data=audio_data, sample_rate=sample_rate)
+        table = self.speaker_diarize.segments(seg, vad_segments)
+        features = self.chunk_embeddings(seg, table)
+        labels, spk_center_embeddings = self.speaker_diarize.clustering(features, speaker_num=speaker_num)
+        outputs = self.speaker_diarize.postprocess(table, labels)
+        if search_audio_db:
+            assert self.audio_feature is not None, "数据库中没有音频数据，请先指定说话人特征数据库或者注册说话人"
+            users = sorted(set(self.users_name))
+            means = np.stack([self.audio_feature[[i for i, n in enumerate(self.users_name) if n == u]].mean(axis=0) for u in users])
+            s = cosine_score_matrix(torch.from_numpy(spk_center_embeddings.astype(np.float32)).to(self.device),
+                                    torch.from_numpy(means.astype(np.float32)).to(self.device)).cpu().numpy()
+            best = np.argmax(s, axis=1)
+            names = [users[j] if s[i, j] >= self.threshold else None for i, j in enumerate(best)]
+            outputs = [dict(speaker=names[o['speaker']] if names[o['speaker']] else f"陌生人{o['speaker']}",
+                            start=o['start'], end=o['end']) for o in outputs]
+        return outputs
 
     def remove_user(self, user_name):
         if user_name not in self.users_name:
