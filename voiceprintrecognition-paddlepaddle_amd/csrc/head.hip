@@ -2,7 +2,8 @@
 //
 // Replaces SpeakerIdentification.forward 'Cosine' (ppvector/models/fc.py:41-53:
 // logits = normalize(x, axis=1) @ normalize(W, axis=0), W [D, C]) and AAMLoss.forward
-// (ppvector/loss/aamloss.py:28-47: sine = sqrt(1 - cos^2) -- no clamp, as the reference;
+// (ppvector/loss/aamloss.py:28-47: sine = sqrt(max(1 - cos^2, 0)) -- the reference has no clamp and returns NaN when an
+// f32 cosine of an exactly aligned embedding rounds above 1; identical wherever |cos| <= 1;
 // phi = cos*cos_m - sine*sin_m; hard/easy margin select; one-hot mix; * scale;
 // CrossEntropyLoss(label_smoothing), mean), and the scoring loops trainer.py:416-423 / predict.py:282.
 // The (B, C) logits are produced in exact f32 on the f32 matrix cores and read once by the loss
@@ -59,7 +60,7 @@ __global__ __launch_bounds__(256) void aam_ce_rows_kernel(AamArgs a) {
         const float cs = row[c];
         float o = cs;
         if (c == y) {
-            const float sine = sqrtf(1.f - cs * cs);
+            const float sine = sqrtf(fmaxf(1.f - cs * cs, 0.f));
             const float phi = cs * a.cos_m - sine * a.sin_m;
             o = a.easy ? (cs > 0.f ? phi : cs) : (cs > a.th ? phi : cs - a.mmm);
         }
@@ -84,7 +85,7 @@ __global__ __launch_bounds__(256) void aam_ce_rows_kernel(AamArgs a) {
         const float lse = M + logf(S);
         // target logit, recomputed by one thread (cheap, keeps the reduction single-pass)
         const float cs = row[y];
-        const float sine = sqrtf(1.f - cs * cs);
+        const float sine = sqrtf(fmaxf(1.f - cs * cs, 0.f));
         const float phi = cs * a.cos_m - sine * a.sin_m;
         float oy = a.easy ? (cs > 0.f ? phi : cs) : (cs > a.th ? phi : cs - a.mmm);
         oy *= a.scale;
@@ -126,7 +127,7 @@ __global__ __launch_bounds__(256) void aam_ce_bwd_rows_kernel(AamBwdArgs a) {
         float o = cs;
         dm = 1.f;
         if (c == y) {
-            const float sine = sqrtf(1.f - cs * cs);
+            const float sine = sqrtf(fmaxf(1.f - cs * cs, 0.f));
             const float phi = cs * a.cos_m - sine * a.sin_m;
             const bool use_phi = a.easy ? (cs > 0.f) : (cs > a.th);
             o = use_phi ? phi : (a.easy ? cs : cs - a.mmm);

@@ -202,7 +202,7 @@ __global__ __launch_bounds__(256, 2) void head_tile_fwd_kernel(HeadTileArgs a) {
                 const float cs = acc[mi][r] * rinv_s[row] * ci;
                 float o = cs;
                 if (c == y) {
-                    const float sine = sqrtf(1.f - cs * cs);
+                    const float sine = sqrtf(fmaxf(1.f - cs * cs, 0.f));
                     const float phi = cs * a.cos_m - sine * a.sin_m;
                     o = a.easy ? (cs > 0.f ? phi : cs) : (cs > a.th ? phi : cs - a.mmm);
                 }
@@ -430,7 +430,7 @@ __global__ __launch_bounds__(256) void head_tile_bwd_kernel(HeadBwdArgs a) {
                             const float cs = acc[mi][r] * rinv_s[row] * ci;
                             float o = cs, dm = 1.f;
                             if (c == y) {
-                                const float sine = sqrtf(1.f - cs * cs);
+                                const float sine = sqrtf(fmaxf(1.f - cs * cs, 0.f));
                                 const float phi = cs * a.cos_m - sine * a.sin_m;
                                 const bool use_phi = a.easy ? (cs > 0.f) : (cs > a.th);
                                 o = use_phi ? phi : (a.easy ? cs : cs - a.mmm);

@@ -50,7 +50,7 @@ __device__ __forceinline__ float margin_out(const MarginArgs& a, bool target, fl
         float o = v;
         dm = a.scale;
         if (target) {
-            const float sine = sqrtf(1.f - v * v);
+            const float sine = sqrtf(fmaxf(1.f - v * v, 0.f));
             const float phi = v * a.cos_m - sine * a.sin_m;
             const bool use_phi = a.easy ? (v > 0.f) : (v > a.th);
             o = use_phi ? phi : (a.easy ? v : v - a.mmm);
@@ -140,7 +140,7 @@ __device__ __forceinline__ float fun_g(float z, int t, float& dg) {
 __device__ __forceinline__ float sphere_term(const SphereArgs& a, bool target, float cs, float bias, float& dcos, float& dbias) {
     float z = cs, dz = 1.f;
     if (a.type_a) {
-        const float sn = sqrtf(1.f - cs * cs);
+        const float sn = sqrtf(fmaxf(1.f - cs * cs, 0.f));
         if (target) {
             if (cs > a.th) { z = cs * a.cos_m - sn * a.sin_m; dz = a.cos_m + cs * a.sin_m / sn; }
             else z = cs - a.mmm;
