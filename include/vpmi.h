@@ -179,10 +179,24 @@ typedef struct {
 int vp_conv1d_tiles_m(int B, int T_out);            /* rows of the psum arrays                     */
 int vp_conv1d_nseg(int T_out);                      /* utterance segments per M-tile               */
 int vp_conv1d_fwd(vp_ctx* ctx, const vp_conv1d_desc* d, vp_stream stream);
-/* Tuning knob (not part of the reference surface): K-loop schedule of the 256-wide bf16 kernel vp_conv1d_fwd dispatches the
- * wide layers to -- -1 = default, 0 = never (128-wide kernel), 1..3 = the two-stage schedules, 4 = half-tile
- * ring, 5 = half-tile ring with resident workgroups (csrc/conv_gemm.hip).  Process-wide; returns the previous value; out-of-range values only query.  Results
- * are identical for every schedule. */
+/* vp_conv1d_plan: the launch vp_conv1d_fwd makes for this descriptor, host only (no device call; the tensor pointers are checked
+ *   for NULL as vp_conv1d_fwd checks them and never dereferenced).  Runs the same validation and the same plan function and returns
+ *   what vp_conv1d_fwd would return up to the launch.  On VP_OK: *kernel = the kernel family (VP_CONV_K*), *tile_n = columns of a
+ *   tile (32 / 64 / 128 / 256; its rows are 128, or 256 for the two VP_CONV_K256_* families), a grid of *tiles_m x *tiles_n
+ *   tiles walked in groups of *group_m row tiles, *launches = batch slices (1 unless the activations exceed the 32-bit buffer
+ *   offsets; the other outputs then describe the first slice).  Any output pointer may be NULL. */
+enum { VP_CONV_K128 = 0,             /* 128-row tiles of 128 / 64 / 32 columns, every precision and mode                         */
+       VP_CONV_K256_TWO_STAGE = 1,   /* bf16, 256 x 256 tiles, LDS-DMA into two 64 KB stages (tapped and strided 1x1 layers)      */
+       VP_CONV_K256_RING = 2,        /* bf16, 256 x 256 tiles, half-tile LDS-DMA ring (1x1 layers)                                */
+       VP_CONV_K128X256_RING = 3 };  /* bf16 or hl32, 128 x 256 tiles, half-tile ring, two workgroups per CU (1x1 layers)         */
+int vp_conv1d_plan(const vp_conv1d_desc* d, int* kernel, int* tile_n, int* tiles_m, int* tiles_n, int* group_m, int* launches);
+/* Tuning knob (not part of the reference surface): which wide-tile kernel vp_conv1d_fwd gives the wide bf16 / hl32 layers
+ * (csrc/conv_gemm.hip): -1 = default (= 6); 0 = never (VP_CONV_K128 everywhere); 3 = VP_CONV_K256_TWO_STAGE; 4 = VP_CONV_K256_RING;
+ * 6 = VP_CONV_K128X256_RING; 7 = 6 for K <= 1024, else 4.  Under 4, 6 and 7 the tapped layers and the strided / padded 1x1
+ * layers take the two-stage kernel.  1 and 2 (the interleaved and ping-pong K-loops) and 5 (resident workgroups) name
+ * schedules that are no longer built: 1 and 2 run as 3, 5 runs as 4.  VPMI_CONV256 presets it (the variable is not range-checked:
+ * a value below -1 acts as -1, one above 7 as 3).  Process-wide; returns the previous value; values outside -1..7 only query.
+ * Results are identical for every schedule. */
 int vp_conv256_select(int schedule);
 
 /* mean / std over time from the conv1d partial sums: stats[b][0:C] = mean, stats[b][C:2C] = std,

@@ -1,7 +1,8 @@
-"""CPU tests of the split-precision engine's two host-side decisions (no GPU needed: neither entry point touches the device):
-the time-segment plan of the fused Res2 chain (vp_res2_chain_x3_plan, csrc/res2_x3.hip: rx_plan) and the ECAPA driver's choice between
-its split-plane fast path and the generic split-precision path (vp_ecapa_x3_fast_path, csrc/ecapa.hip: ecapa_hl_ok), each against a
-NumPy / Python restatement of its contract."""
+"""CPU tests of the engine's three host-side decisions (no GPU needed: none of the entry points touches the device): the time-segment
+plan of the fused Res2 chain (vp_res2_chain_x3_plan, csrc/res2_x3.hip: rx_plan), the ECAPA driver's choice between its split-plane
+fast path and the generic split-precision path (vp_ecapa_x3_fast_path, csrc/ecapa.hip: ecapa_hl_ok), each against a NumPy / Python
+restatement of its contract, and the kernel family and tile geometry vp_conv1d_fwd gives a layer (vp_conv1d_plan,
+csrc/conv_gemm.hip: conv_plan) against a table of layer shapes and the properties every plan must have."""
 import ctypes as C
 import functools
 import os
@@ -232,3 +233,272 @@ def test_ecapa_x3_fast_path_predicate_sweep(N):
             for T in Ts:
                 got = N.lib().vp_ecapa_x3_fast_path(C.byref(W), B, T)
                 assert bool(got) == ref_fast_path(N, W, B, T), (dils, B, T, got)
+
+
+# ------------------------------------------------------------------------------------------- the conv forward's kernel choice
+CONV_ENV = ('VPMI_CONV256', 'VPMI_RING_MIN_COUT', 'VPMI_HL_BN128', 'VPMI_BN64', 'VPMI_GROUP_M')
+TILE_ROWS = {0: 128, 1: 256, 2: 256, 3: 128}        # VP_CONV_K128, _K256_TWO_STAGE, _K256_RING, _K128X256_RING
+GROUP_CLAMP = {0: 16, 1: 16, 2: 16, 3: 32}
+
+
+@pytest.fixture
+def conv(N):
+    """The library for the tests whose expected plans are those of the default switches.  The switches are A/B knobs the library
+    reads once per process, so with one of them exported these tests cannot say anything about the defaults: they fail, naming the
+    variable.  (test_conv1d_plan_batch_slices and test_conv1d_plan_error_paths hold under any setting and do not come through here.)"""
+    exported = [v for v in CONV_ENV if os.environ.get(v) is not None]
+    assert not exported, f'unset {", ".join(exported)}: the plans pinned here are those of the default conv dispatch switches'
+    assert (N.VP_CONV_K128, N.VP_CONV_K256_TWO_STAGE, N.VP_CONV_K256_RING, N.VP_CONV_K128X256_RING) == (0, 1, 2, 3)
+    return N
+
+
+def conv_desc(N, dt_in, dt_out, B, T_in, Cin, Cout, kw=1, dil=1, stride=1, T_out=None, pad_mode=None, psum=False, ldx=None, **more):
+    """A valid vp_conv1d_desc with dummy non-null tensor pointers (the plan reads the struct, never through it): 'same' padding for
+    tapped layers (reflect unless pad_mode says otherwise), none for 1x1 layers."""
+    d = N.Conv1dDesc()
+    d.dtype_in, d.dtype_out = dt_in, dt_out
+    d.B, d.T_in, d.T_out = B, T_in, T_in if T_out is None else T_out
+    d.Cin, d.Cout, d.KW, d.dilation, d.stride = Cin, Cout, kw, dil, stride
+    d.pad_mode = pad_mode if pad_mode is not None else (N.VP_PAD_REFLECT if kw > 1 else N.VP_PAD_NONE)
+    d.pad_left = dil * (kw - 1) // 2 if d.pad_mode != N.VP_PAD_NONE else 0
+    d.x, d.w, d.y = _PTR, _PTR + 64, _PTR + 128
+    d.ldx, d.ldy = Cin if ldx is None else ldx, Cout
+    if psum:
+        d.psum = d.psumsq = _PTR + 192
+    if N.VP_HL32 in (dt_in, dt_out):
+        d.mfma_bf16 = 2
+    for k, v in more.items():
+        setattr(d, k, v)
+    return d
+
+
+def conv_plan(N, d):
+    """(rc, kernel, tile_n, tiles_m, tiles_n, group_m, launches)"""
+    out = [C.c_int(-1) for _ in range(6)]
+    rc = N.lib().vp_conv1d_plan(C.byref(d), *[C.byref(o) for o in out])
+    return (rc,) + tuple(o.value for o in out)
+
+
+def _table(N):
+    """name -> (descriptor, kernel, tile_n, tiles_m, tiles_n, group_m) at the default schedule; None = not pinned.  B 57 x T 298 =
+    16 986 rows = 133 tiles of 128 = 67 of 256; the wide tiles want 128 x 32 (K128X256_RING) or 256 x 64 = 16 384 rows."""
+    BF, F32, HL = N.VP_BF16, N.VP_F32, N.VP_HL32
+    K128, TWO, RING, R128 = 0, 1, 2, 3
+    return {
+        'bf16 1x1 512->512': (conv_desc(N, BF, BF, 57, 298, 512, 512), R128, 256, 133, 2, 32),
+        'bf16 1x1 512->512 psum': (conv_desc(N, BF, BF, 57, 298, 512, 512, psum=True), R128, 256, 133, 2, 32),
+        'bf16->f32 1x1 512->512 (data gradient)': (conv_desc(N, BF, F32, 57, 298, 512, 512), R128, 256, 133, 2, 32),
+        'bf16 taps 64->256 k3 dil 2': (conv_desc(N, BF, BF, 66, 250, 64, 256, kw=3, dil=2), TWO, 256, 65, 1, 16),         # MODE_TAPS
+        'bf16 taps 80->512 k5': (conv_desc(N, BF, BF, 70, 241, 80, 512, kw=5), TWO, 256, 66, 2, 16),                       # MODE_TAPS_GEN
+        'bf16 taps 64->256 k3 dil 2, 15 000 rows': (conv_desc(N, BF, BF, 60, 250, 64, 256, kw=3, dil=2), K128, 128, 118, 2, 16),
+        'bf16 1x1 512->512 stride 2': (conv_desc(N, BF, BF, 57, 596, 512, 512, stride=2, T_out=298), TWO, 256, 67, 2, 16),
+        'bf16 1x1 1536->128': (conv_desc(N, BF, BF, 57, 298, 1536, 128), K128, 128, 133, 1, 16),
+        'hl32 1x1 1536->128': (conv_desc(N, HL, HL, 57, 298, 1536, 128), K128, 64, 133, 2, 16),
+        'hl32 1x1 512->512': (conv_desc(N, HL, HL, 57, 298, 512, 512), R128, 256, 133, 2, 32),
+        'f32 64->32': (conv_desc(N, F32, F32, 2, 100, 64, 32), K128, 32, 2, 1, 16),
+        'f32 1x1 pro 64->128': (conv_desc(N, F32, F32, 2, 100, 64, 128, pro_scale=_PTR, pro_shift=_PTR), K128, 64, None, 2, None),
+    }
+
+
+class _selected:
+    """with _selected(N, s): vp_conv256_select(s) inside, the previous selection restored after."""
+
+    def __init__(self, N, sched):
+        self.N, self.sched = N, sched
+
+    def __enter__(self):
+        self.prev = self.N.lib().vp_conv256_select(self.sched)
+
+    def __exit__(self, *exc):
+        self.N.lib().vp_conv256_select(self.prev)
+
+
+def test_conv1d_plan_table(conv):
+    """The plan of the layer shapes the backbones and the training step run, at the default schedule."""
+    for name, (d, *want) in _table(conv).items():
+        rc, *got = conv_plan(conv, d)
+        assert rc == conv.VP_OK, (name, rc)
+        assert got[5] == 1, (name, got)
+        for what, g, w in zip(('kernel', 'tile_n', 'tiles_m', 'tiles_n', 'group_m'), got, want):
+            assert w is None or g == w, (name, what, g, w)
+    # any output pointer may be NULL
+    d = _table(conv)['bf16 1x1 512->512'][0]
+    tm = C.c_int()
+    assert conv.lib().vp_conv1d_plan(C.byref(d), None, None, C.byref(tm), None, None, None) == conv.VP_OK and tm.value == 133
+    assert conv.lib().vp_conv1d_plan(C.byref(d), None, None, None, None, None, None) == conv.VP_OK
+
+
+def test_conv1d_plan_under_select(conv):
+    """vp_conv256_select: 4 = K256_RING (f32 output then falls to K128), 3 = K256_TWO_STAGE, 1 and 2 run as 3, 5 as 4, 7 = 6 for
+    K <= 1024 else 4, 0 = K128 everywhere; the call returns the previous selection and ignores values outside -1 .. 7."""
+    N, lib = conv, conv.lib()
+    table = _table(N)
+    wide = conv_desc(N, N.VP_BF16, N.VP_BF16, 57, 298, 1536, 1536)
+    prev = lib.vp_conv256_select(-1)
+    try:
+        assert lib.vp_conv256_select(8) == -1 and lib.vp_conv256_select(-2) == -1          # out of range: query only
+        plans = {}
+        for s in range(0, 8):
+            assert lib.vp_conv256_select(s) == (s - 1 if s else -1)
+            plans[s] = {name: conv_plan(N, d) for name, (d, *_) in table.items()}
+            plans[s]['wide'] = conv_plan(N, wide)
+        assert lib.vp_conv256_select(-1) == 7
+        assert plans[4]['bf16 1x1 512->512'] == (N.VP_OK, 2, 256, 67, 2, 16, 1)
+        assert plans[4]['bf16->f32 1x1 512->512 (data gradient)'] == (N.VP_OK, 0, 128, 133, 4, 16, 1)
+        assert plans[3]['bf16 1x1 512->512'] == (N.VP_OK, 1, 256, 67, 2, 16, 1)
+        assert plans[1] == plans[3] and plans[2] == plans[3]
+        assert plans[5] == plans[4]
+        assert plans[6] == {**{name: conv_plan(N, d) for name, (d, *_) in table.items()}, 'wide': conv_plan(N, wide)}      # -1 = 6
+        assert plans[6]['wide'] == (N.VP_OK, 3, 256, 133, 6, 10, 1) and plans[4]['wide'] == (N.VP_OK, 2, 256, 67, 6, 5, 1)
+        assert plans[7]['bf16 1x1 512->512'] == plans[6]['bf16 1x1 512->512']               # K = 512
+        assert plans[7]['wide'] == plans[4]['wide']                                         # K = 1536
+        # the tapped and the strided layers are on the two-stage kernel under 3, 4, 6 and 7 alike
+        for name in ('bf16 taps 64->256 k3 dil 2', 'bf16 taps 80->512 k5', 'bf16 1x1 512->512 stride 2'):
+            assert len({plans[s][name] for s in (3, 4, 6, 7)}) == 1 and plans[3][name][1] == 1, name
+        for name, p in plans[0].items():
+            assert p[0] == N.VP_OK and p[1] == 0, (name, p)
+        assert plans[0]['hl32 1x1 512->512'] == (N.VP_OK, 0, 128, 133, 4, 16, 1)
+    finally:
+        lib.vp_conv256_select(prev)
+
+
+def conv_grid(N, n=2000, seed=20):
+    """n seeded valid descriptors: 1x1 / tapped / strided 1x1 / gated / input-prologue / 2-D layers in every precision pair the
+    library builds, with and without fused time sums, around the row and column thresholds of the wide tiles."""
+    rng = np.random.RandomState(seed)
+    BF, F32, HL = N.VP_BF16, N.VP_F32, N.VP_HL32
+    pairs = ((BF, BF), (BF, F32), (F32, F32), (HL, HL), (HL, F32), (F32, HL))
+    pick = lambda xs: xs[rng.randint(len(xs))]
+    out = []
+    while len(out) < n:
+        dt_in, dt_out = pick(pairs)
+        hl = HL in (dt_in, dt_out)
+        kind = pick(('1x1', '1x1', 'taps', 'taps', 'strided', 'gate', 'pro', '2d'))
+        if hl and kind in ('gate', 'pro', '2d'):
+            kind = '1x1'
+        B, T = int(pick((1, 2, 8, 13, 32, 55, 57, 64, 66, 130))), int(pick((24, 100, 127, 128, 200, 250, 298, 512)))
+        Cin = int(pick((32, 64, 96, 128, 256, 512, 1024, 1536) + (() if hl else (80, 40))))
+        Cout = int(pick((32, 64, 96, 128, 224, 256, 320, 512, 1536)))
+        psum = bool(rng.randint(2)) and kind != '2d' and (T // 2 if kind == 'strided' else T) >= 22      # (<= 8 segments per M-tile)
+        if dt_in == HL and dt_out == F32:                    # built on the ring only: wide 1x1 layers
+            kind, Cout, B, T = '1x1', max(Cout, 256), max(B, 32), max(T, 128)
+        kw = dict(psum=psum)
+        if dt_in == F32 and not hl:
+            kw['mfma_bf16'] = int(rng.randint(4))
+        if kind == 'taps':
+            kw.update(kw=int(pick((3, 5))), dil=int(pick((1, 2, 3))), pad_mode=pick((N.VP_PAD_REFLECT, N.VP_PAD_ZERO)))
+        elif kind == 'strided':
+            kw.update(stride=2, T_out=T // 2)
+        elif kind == 'gate':
+            kw.update(gate=_PTR, gate_len=100, gate_nseg=(T + 99) // 100)
+        elif kind == 'pro':
+            kw.update(pro_scale=_PTR, pro_shift=_PTR)
+        elif kind == '2d':
+            kw.update(kw=9, KF=3, F_in=10, F_out=10, stride_f=1, pad_f=1, pad_mode=N.VP_PAD_ZERO)
+        d = conv_desc(N, dt_in, dt_out, B, T, Cin, Cout, **kw)
+        if kind == '2d':
+            d.pad_left = 1
+        out.append((kind, d))
+    return out
+
+
+def test_conv1d_plan_grid_properties(conv):
+    """Every plan of ~2 000 valid descriptors, under every selection: the tile grid covers the M x N problem with no empty row or
+    column of tiles, the group size is within its family's clamp, f32 output never gets a 256-row family, gated and 2-D layers
+    always get K128, and fused time sums with T_out < 128 never get a wide family (its epilogue writes two utterance segments
+    per 128 rows)."""
+    N, lib = conv, conv.lib()
+    grid = conv_grid(N)
+    seen = set()
+    prev = lib.vp_conv256_select(-1)
+    try:
+        for s in (-1, 0, 1, 2, 3, 4, 5, 6, 7):
+            lib.vp_conv256_select(s)
+            for kind, d in grid:
+                rc, k, tn, tm_, tn_, gm, nl = conv_plan(N, d)
+                what = (s, kind, d.dtype_in, d.dtype_out, d.B, d.T_in, d.T_out, d.Cin, d.Cout, d.KW, bool(d.psum), (k, tn, tm_, tn_, gm, nl))
+                if s == 0 and (d.dtype_in, d.dtype_out) == (N.VP_HL32, N.VP_F32):
+                    assert rc == N.VP_EUNSUP, (rc, what)         # built on the ring only
+                    continue
+                assert rc == N.VP_OK and nl == 1, (rc, what)
+                M = d.B * d.T_out * (d.F_out if kind == '2d' else 1)
+                rows = TILE_ROWS[k]
+                assert tn in ((32, 64, 128) if k == 0 else (256,)), what
+                assert tm_ * rows >= M > (tm_ - 1) * rows, what
+                assert tn_ * tn >= d.Cout > (tn_ - 1) * tn, what
+                assert 1 <= gm <= GROUP_CLAMP[k], what
+                if d.dtype_out == N.VP_F32:
+                    assert rows == 128, what
+                if kind in ('gate', '2d') or s == 0:
+                    assert k == 0, what
+                if d.psum and d.T_out < 128:
+                    assert k == 0, what
+                if k in (2, 3):                              # the rings: plain 1x1 layers only
+                    assert d.KW == 1 and d.stride == 1 and d.T_in == d.T_out and kind != 'pro', what
+                if k != 0:
+                    assert d.dtype_in in (N.VP_BF16, N.VP_HL32) and d.Cout >= 256 and M >= 128 * 32, what
+                seen.add((s if s in (0, 3, 4, 6) else None, k))
+    finally:
+        lib.vp_conv256_select(prev)
+    assert {(0, 0), (3, 0), (3, 1), (4, 1), (4, 2), (6, 1), (6, 3), (4, 3), (3, 3)} <= seen, sorted(seen, key=str)     # (hl32: always 3)
+
+
+def test_conv1d_plan_batch_slices(N):
+    """Activations past the 32-bit buffer offsets run as launches over slices of bc utterances: bc = the most whose activations stay
+    under 0xe0000000 bytes, rounded down -- when time sums are fused -- to a count whose rows end on an M-tile boundary of the
+    partial-sum arrays (bc T_out % 128 == 0).  The plan reports the launches and describes the first slice.  (f32 layers: no
+    dispatch switch touches them.)"""
+    for B, T, psum in ((128, 20000, True), (128, 20000, False), (8000, 298, True), (8000, 298, False)):
+        d = conv_desc(N, N.VP_F32, N.VP_F32, B, T, 64, 64, ldx=512, psum=psum)
+        assert B * T * 512 * 4 > 1 << 32
+        rc, k, tn, tm_, tn_, gm, nl = conv_plan(N, d)
+        assert (rc, k, tn, tn_) == (N.VP_OK, 0, 64, 1), (B, T, psum, rc, k, tn, tn_)
+        bc = 0xe0000000 // (T * 512 * 4)
+        if psum:
+            q = 128 // np.gcd(T, 128)
+            bc = bc // q * q
+            assert bc * T % 128 == 0 and tm_ * 128 == bc * T, (B, T, bc, tm_)
+        assert 1 <= bc < B and bc * T * 512 * 4 < 1 << 32
+        assert nl == -(-B // bc) and nl > 1, (B, T, psum, nl, bc)
+        assert tm_ == -(-bc * T // 128), (B, T, psum, tm_, bc)
+    d = conv_desc(N, N.VP_F32, N.VP_F32, 2, 4200000, 512, 512)          # the first utterance alone is past 4 GiB: no slice helps
+    assert conv_plan(N, d)[0] == N.VP_EUNSUP
+
+
+def test_conv1d_plan_error_paths(N):
+    """vp_conv1d_plan runs vp_conv1d_fwd's validation: the descriptors tests/test_gpu_kernels.py sees refused before any launch
+    (test_conv1d_rejects_bad_shapes, test_conv1d_mfma_mode_contract) and a few more return the same code here, and leave the
+    outputs alone.  None of it depends on a dispatch switch."""
+    BF, F32, HL = N.VP_BF16, N.VP_F32, N.VP_HL32
+    E, U = N.VP_EINVAL, N.VP_EUNSUP
+    cases = [
+        ('Cin % 8 != 0 (bf16)', conv_desc(N, BF, BF, 1, 8, 20, 16, kw=3), None, None, E),
+        ('reflect pad >= T', conv_desc(N, F32, F32, 1, 2, 16, 16, kw=3, dil=4), None, None, E),
+        ('one utterance past 4 GiB', conv_desc(N, BF, BF, 1, 4200000, 512, 512, pad_mode=N.VP_PAD_REFLECT), None, None, U),
+        ('empty batch', conv_desc(N, BF, BF, 0, 4200000, 512, 512, pad_mode=N.VP_PAD_REFLECT), None, None, E),
+        ('null x', conv_desc(N, BF, BF, 2, 100, 64, 64), 'x', None, E),
+        ('null w', conv_desc(N, BF, BF, 2, 100, 64, 64), 'w', None, E),
+        ('null y', conv_desc(N, BF, BF, 2, 100, 64, 64), 'y', None, E),
+        ('bad dtype', conv_desc(N, BF, BF, 2, 100, 64, 64), 'dtype_in', 9, E),
+        ('f32 -> bf16', conv_desc(N, F32, BF, 2, 100, 64, 64), None, None, U),
+        ('hl32 Cin % 32', conv_desc(N, HL, HL, 2, 100, 48, 64), None, None, E),
+        ('hl32 tapped 2-D', conv_desc(N, HL, HL, 2, 100, 64, 64, KF=3, kw=9, F_in=4, F_out=4, stride_f=1), None, None, U),
+        ('hl32 -> f32 off the ring', conv_desc(N, HL, F32, 2, 100, 64, 64), None, None, U),
+        ('time sums with T_out 16', conv_desc(N, F32, F32, 4, 16, 64, 64, psum=True), None, None, U),
+        ('2-D with time sums', conv_desc(N, F32, F32, 2, 20, 16, 16, kw=9, KF=3, F_in=4, F_out=4, stride_f=1, pad_mode=N.VP_PAD_ZERO,
+                                         psum=True), None, None, U),
+        ('un-padded window leaves the input', conv_desc(N, F32, F32, 2, 20, 16, 16, kw=3, pad_mode=N.VP_PAD_NONE), None, None, E),
+        ('ysplit without y2', conv_desc(N, F32, F32, 2, 20, 16, 16, ysplit=8), None, None, E),
+        ('gate without segments', conv_desc(N, F32, F32, 2, 20, 16, 16, gate=_PTR), None, None, E),
+        ('prologue on a tapped conv', conv_desc(N, F32, F32, 2, 20, 16, 16, kw=3, pro_scale=_PTR, pro_shift=_PTR), None, None, E),
+    ]
+    for dt, cin, kw in ((F32, 64, 3), (HL, 64, 1)):                      # test_conv1d_mfma_mode_contract
+        for mode in (-1, 4, 7) + ((3,) if dt == HL else ()):
+            cases.append((f'mfma_bf16 {mode} dtype {dt}', conv_desc(N, dt, dt, 2, 300, cin, 64, kw=kw), 'mfma_bf16', mode, E))
+    for name, d, field, value, want in cases:
+        if field:
+            setattr(d, field, value)
+        assert conv_plan(N, d) == (want, -1, -1, -1, -1, -1, -1), name
+    assert N.lib().vp_conv1d_plan(None, None, None, None, None, None, None) == E
+    ok = conv_desc(N, HL, HL, 2, 300, 64, 64)                            # ... and the same descriptors in mode 2 plan
+    assert conv_plan(N, ok)[:2] == (N.VP_OK, 0)

@@ -1,4 +1,9 @@
-// 256 x 256 x 64 conv GEMM for the wide bf16 layers (1x1 / tapped 1-D, Cin % 64 == 0).
+// The wide-tile conv GEMMs (256 output channels per tile, operands by LDS-DMA), three kernel families (conv_gemm_impl.h: ConvKernel):
+//   K256_TWO_STAGE  conv_gemm256_kernel            256 x 256, two 64 KB stages: 1x1, tapped (MODE_TAPS) and tapped with Cin % 64 != 0
+//                                                  (MODE_TAPS_GEN) bf16 layers -- described first, below
+//   K256_RING       conv_gemm256_ring_kernel       256 x 256, half-tile ring: plain 1x1 bf16 layers
+//   K128X256_RING   conv_gemm128x256_ring_kernel   128 x 256, half-tile ring, two workgroups per CU: plain 1x1 layers, bf16 or hl32
+// Which layer gets which: conv_plan() in conv_gemm.hip.
 //
 // Why a second kernel: the 128 x 128 kernel (conv_gemm_impl.h) moves 64 FLOP per byte staged and
 // pays a ds_write_b128 pass (~79 B/clk/CU) for every byte, so its LDS pipe is as busy as its MFMA
@@ -8,7 +13,8 @@
 // wave's 64 x 16 B linearly, so the XOR swizzle that keeps ds_read_b128 conflict-free is applied to
 // the per-lane SOURCE chunk (and again on the read) instead of the destination.  Out-of-range rows /
 // padding taps use out-of-range buffer offsets: the DMA writes zeros.
-// Two LDS stages of 64 KB; per K-step: wait own DMAs -> barrier -> issue next stage -> 64 MFMAs/wave.
+// K256_TWO_STAGE: two LDS stages of 64 KB; per K-step: wait own DMAs -> barrier -> 64 MFMAs/wave with the next stage's DMAs issued
+// between them (role-split: see the loop).  The ring kernels have their own headers further down.
 // Epilogue semantics are those of conv_gemm_impl.h (same ConvArgs, same psum layout per 128 rows).
 #include "conv_gemm_impl.h"
 
@@ -17,11 +23,10 @@
 namespace {
 
 constexpr int T2 = 256;                      // tile edge (positions and channels)
-constexpr int MODE_TAPS_GEN = 4;             // tapped 1-D conv with Cin % 64 != 0: a K-step may straddle taps (role-split schedule only)
 constexpr int STAGE2 = 2 * T2 * ROWB;        // X panel + W panel
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
-// Epilogue of one tile, shared by every K-loop schedule.  Entered by all threads with each wave's 64 x 128 accumulators in
+// Epilogue of one tile, shared by the three kernels below.  Entered by all threads with each wave's 64 x 128 accumulators in
 // registers, after a barrier behind which the LDS range [ebase, ebase + NW x 64 x 272 + NW x 2 KB) is dead.
 //   y = act2( bn( act( acc + bias + rowbias ) ) + res );  aux = y + add_in;  psum/psumsq over (y - shift)
 // (conv_gemm_impl.h semantics, no gate).  Written as ROLLED loops over an LDS image of the accumulators: the fully
@@ -348,13 +353,13 @@ __device__ __forceinline__ void epilogue256(const ConvArgs& a, f32x4 (&acc)[4][8
     }
 }
 
-template <int MODE, int SCHED>
+template <int MODE>
 __global__ __launch_bounds__(512) void conv_gemm256_kernel(const ConvArgs a) {
     constexpr int MI = 4, NI = 8;            // per wave: 64 positions x 128 channels
     extern __shared__ __attribute__((aligned(16))) char smem[];
 #ifdef VP_TIMING
     const unsigned long long tk0 = wall_clock64();
-    unsigned long long tk1 = 0, twait = 0, tbar = 0, ck1 = 0;
+    unsigned long long tk1 = 0, ck1 = 0;
 #endif
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -376,62 +381,39 @@ __global__ __launch_bounds__(512) void conv_gemm256_kernel(const ConvArgs a) {
     const __amdgpu_buffer_rsrc_t xsrd = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.x), 0, a.x_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t wsrd = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.w), 0, a.w_bytes, 0x00020000);
 
-    // staging: wave wv fills rows [32 wv, 32 wv + 32) of both panels, 8 rows x 128 B per DMA; lane l
-    // lands at row (l >> 3), slot (l & 7) and therefore fetches chunk slot ^ row
+    // staging: 8 rows x 128 B per DMA; lane l lands at row (l >> 3), slot (l & 7) and therefore fetches chunk slot ^ row
     const int srow = lane >> 3;
     const unsigned cb = (unsigned)((lane & 7) ^ srow) << 4;
     const bool zero_pad = a.pad_mode == VP_PAD_ZERO;
     const unsigned ldxb = (unsigned)a.ldx * 2u;
-    unsigned rowoff[4], rowfix[4], woff[4];
-    int tpos[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int m = m0 + wv * 32 + i * 8 + srow;
-        const bool ok = m < a.M;
-        const int mm = ok ? m : 0;
-        const int b = mm / a.T_out;
-        const int t = mm - b * a.T_out;
-        tpos[i] = t * a.stride - a.pad_left;
-        rowoff[i] = ok ? ((unsigned)(b * a.T_in) * (unsigned)a.ldx + (unsigned)a.xoff) * 2u : OOB;
-        const int traw = tpos[i];
-        int ts = traw < 0 ? -traw : traw;
-        ts = ts >= a.T_in ? 2 * (a.T_in - 1) - ts : ts;
-        const bool inr = traw >= 0 && traw < a.T_in;
-        rowfix[i] = (ok && (inr || !zero_pad)) ? rowoff[i] + (unsigned)ts * ldxb + cb : OOB;
-        const int n = n0 + wv * 32 + i * 8 + srow;
-        woff[i] = n < a.N ? (unsigned)n * (unsigned)a.K * 2u + cb : OOB;
-    }
-
-    // SCHED 2 staging roles: waves 0..3 stage the X panel (rows 64 (wv & 3) + 8 i), waves 4..7 the W panel, and
+    // staging roles: waves 0..3 stage the X panel (rows 64 (wv & 3) + 8 i), waves 4..7 the W panel, and
     // each role issues its 8 pieces inside a different half of the K-step (see the loop below)
     const bool w_role = wv >= 4;
     unsigned qoff[8];
     int qpos[8];
-    if constexpr (SCHED == 2) {
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int r = (wv & 3) * 64 + i * 8 + srow;
-            if (w_role) {
-                const int n = n0 + r;
-                qoff[i] = n < a.N ? (unsigned)n * (unsigned)a.K * 2u + cb : OOB;
-                qpos[i] = 0;
+    for (int i = 0; i < 8; ++i) {
+        const int r = (wv & 3) * 64 + i * 8 + srow;
+        if (w_role) {
+            const int n = n0 + r;
+            qoff[i] = n < a.N ? (unsigned)n * (unsigned)a.K * 2u + cb : OOB;
+            qpos[i] = 0;
+        } else {
+            const int m = m0 + r;
+            const bool ok = m < a.M;
+            const int mm = ok ? m : 0;
+            const int b = mm / a.T_out;
+            const int t = mm - b * a.T_out;
+            qpos[i] = t * a.stride - a.pad_left;
+            const unsigned ro = ok ? ((unsigned)(b * a.T_in) * (unsigned)a.ldx + (unsigned)a.xoff) * 2u : OOB;
+            if constexpr (MODE == MODE_1X1) {
+                const int traw = qpos[i];
+                int ts = traw < 0 ? -traw : traw;
+                ts = ts >= a.T_in ? 2 * (a.T_in - 1) - ts : ts;
+                const bool inr = traw >= 0 && traw < a.T_in;
+                qoff[i] = (ok && (inr || !zero_pad)) ? ro + (unsigned)ts * ldxb + cb : OOB;
             } else {
-                const int m = m0 + r;
-                const bool ok = m < a.M;
-                const int mm = ok ? m : 0;
-                const int b = mm / a.T_out;
-                const int t = mm - b * a.T_out;
-                qpos[i] = t * a.stride - a.pad_left;
-                const unsigned ro = ok ? ((unsigned)(b * a.T_in) * (unsigned)a.ldx + (unsigned)a.xoff) * 2u : OOB;
-                if constexpr (MODE == MODE_1X1) {
-                    const int traw = qpos[i];
-                    int ts = traw < 0 ? -traw : traw;
-                    ts = ts >= a.T_in ? 2 * (a.T_in - 1) - ts : ts;
-                    const bool inr = traw >= 0 && traw < a.T_in;
-                    qoff[i] = (ok && (inr || !zero_pad)) ? ro + (unsigned)ts * ldxb + cb : OOB;
-                } else {
-                    qoff[i] = ro;
-                }
+                qoff[i] = ro;
             }
         }
     }
@@ -471,222 +453,51 @@ __global__ __launch_bounds__(512) void conv_gemm256_kernel(const ConvArgs a) {
         }
     };
 
-    // one DMA piece (8 rows x 128 B of one panel): pieces 0..3 = X rows 8i.., pieces 4..7 = W rows
-    auto stage_piece = [&](int kt, int s, int i) {
-        char* Xs = smem + s * STAGE2 + wv * (32 * ROWB);
-        char* Ws = Xs + T2 * ROWB;
-        const unsigned kb = (unsigned)kt * (unsigned)ROWB;
-        if (i >= 4) {
-            const int w = i - 4;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(wsrd, (lds_ptr_t)(Ws + w * (8 * ROWB)), 16,
-                                                     woff[w] != OOB ? woff[w] + kb : OOB, 0, 0, 0);
-        } else if constexpr (MODE == MODE_1X1) {
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(xsrd, (lds_ptr_t)(Xs + i * (8 * ROWB)), 16,
-                                                     rowfix[i] != OOB ? rowfix[i] + kb : OOB, 0, 0, 0);
-        } else {
-            const int k0 = kt * 64;                     // Cin % 64 == 0: one tap per K-step
-            const int j = k0 / a.Cin;
-            const unsigned cbase = (unsigned)(k0 - j * a.Cin) * 2u + cb;
-            const int traw = tpos[i] + j * a.dilation;
-            int ts = traw < 0 ? -traw : traw;
-            ts = ts >= a.T_in ? 2 * (a.T_in - 1) - ts : ts;
-            const bool inr = traw >= 0 && traw < a.T_in;
-            const bool ok = rowoff[i] != OOB && (inr || !zero_pad);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(xsrd, (lds_ptr_t)(Xs + i * (8 * ROWB)), 16,
-                                                     ok ? rowoff[i] + (unsigned)ts * ldxb + cbase : OOB, 0, 0, 0);
-        }
-    };
-    auto stage = [&](int kt, int s) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) stage_piece(kt, s, i);
-    };
-
     f32x4 acc[MI][NI];
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni) acc[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    [[maybe_unused]] auto compute = [&](int s) {
-        const char* Xs = smem + s * STAGE2;
-        const char* Ws = Xs + T2 * ROWB;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-#ifdef VP_EXP_NOLDS
-            Frag<bf16_t> xf[MI], wf[NI];
-#pragma unroll
-            for (int mi = 0; mi < MI; ++mi) xf[mi].v = __builtin_bit_cast(bf16x8, u32x4{(unsigned)s, (unsigned)mi, 3u, 4u});
-#pragma unroll
-            for (int ni = 0; ni < NI; ++ni) wf[ni].v = __builtin_bit_cast(bf16x8, u32x4{(unsigned)s, (unsigned)ni, 5u, (unsigned)lane});
-#else
-            Frag<bf16_t> xf[MI], wf[NI];
-#pragma unroll
-            for (int mi = 0; mi < MI; ++mi) load_frag(Xs, wm * 64 + mi * 16 + li, ks, g, xf[mi]);
-#pragma unroll
-            for (int ni = 0; ni < NI; ++ni) load_frag(Ws, wn * 128 + ni * 16 + li, ks, g, wf[ni]);
-#endif
-#pragma unroll
-            for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < NI; ++ni) mma(wf[ni], xf[mi], acc[mi][ni]);
-        }
-    };
-
     const int KT = a.KT;
-    if constexpr (SCHED == 2) {
 #pragma unroll
-        for (int i = 0; i < 8; ++i) role_piece(0, 0, i);
-        // Role-split schedule: one barrier per K-step as in SCHED 0, but the two waves of a SIMD issue their
-        // DMA pieces in DIFFERENT halves of the step (waves 0..3: X panel during the ks = 0 MFMAs; waves 4..7:
-        // the L2-resident W panel during the ks = 1 MFMAs).  A wave stalls ~100 cycles per piece at issue (the
-        // vector-memory path takes ~64 B/clk/CU); while it does, its SIMD partner -- which has no DMA in this
-        // half -- keeps the MFMA pipe fed, instead of both stalling together.
-        const int my_half = w_role ? 1 : 0;
-        for (int kt = 0; kt < KT; ++kt) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-#ifdef VP_TIMING
-            if (kt == 0) { tk1 = wall_clock64(); ck1 = clock64(); }
-#endif
-            const bool more = kt + 1 < KT;
-            const char* Xs = smem + (kt & 1) * STAGE2;
-            const char* Ws = Xs + T2 * ROWB;
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                Frag<bf16_t> xf[MI], wf[NI];
-#pragma unroll
-                for (int mi = 0; mi < MI; ++mi) load_frag(Xs, wm * 64 + mi * 16 + li, ks, g, xf[mi]);
-#pragma unroll
-                for (int ni = 0; ni < NI; ++ni) load_frag(Ws, wn * 128 + ni * 16 + li, ks, g, wf[ni]);
-#pragma unroll
-                for (int mi = 0; mi < MI; ++mi) {
-                    if (more && ks == my_half) {
-                        role_piece(kt + 1, (kt + 1) & 1, 2 * mi);
-                        role_piece(kt + 1, (kt + 1) & 1, 2 * mi + 1);
-                    }
-#pragma unroll
-                    for (int ni = 0; ni < NI; ++ni) mma(wf[ni], xf[mi], acc[mi][ni]);
-                }
-            }
-        }
-    } else {
-    stage(0, 0);
-    if constexpr (SCHED == 0) {
+    for (int i = 0; i < 8; ++i) role_piece(0, 0, i);
+    // Role-split schedule: one barrier per K-step, and the two waves of a SIMD issue their
+    // DMA pieces in DIFFERENT halves of the step (waves 0..3: X panel during the ks = 0 MFMAs; waves 4..7:
+    // the L2-resident W panel during the ks = 1 MFMAs).  A wave stalls ~100 cycles per piece at issue (the
+    // vector-memory path takes ~64 B/clk/CU); while it does, its SIMD partner -- which has no DMA in this
+    // half -- keeps the MFMA pipe fed, instead of both stalling together.
+    const int my_half = w_role ? 1 : 0;
     for (int kt = 0; kt < KT; ++kt) {
-        // own DMAs of stage kt have landed; after the barrier so have everyone's, and every wave
-        // is done reading the other buffer (stage kt-1), which the next DMAs overwrite
-#ifdef VP_TIMING
-        const unsigned long long tw0 = wall_clock64();
-#endif
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef VP_TIMING
-        const unsigned long long tw1 = wall_clock64();
-#endif
         __syncthreads();
 #ifdef VP_TIMING
         if (kt == 0) { tk1 = wall_clock64(); ck1 = clock64(); }
-        else { twait += tw1 - tw0; tbar += wall_clock64() - tw1; }
 #endif
-        // the next stage's 8 DMA pieces are spread over this step's MFMA groups: the vector-memory path takes
-        // ~64 B/clk/CU, so a burst of all 64 pieces right after the barrier stalls every wave at issue
         const bool more = kt + 1 < KT;
         const char* Xs = smem + (kt & 1) * STAGE2;
         const char* Ws = Xs + T2 * ROWB;
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             Frag<bf16_t> xf[MI], wf[NI];
-#ifdef VP_EXP_NOLDS
-#pragma unroll
-            for (int mi = 0; mi < MI; ++mi) xf[mi].v = __builtin_bit_cast(bf16x8, u32x4{(unsigned)kt, (unsigned)mi, 3u, 4u});
-#pragma unroll
-            for (int ni = 0; ni < NI; ++ni) wf[ni].v = __builtin_bit_cast(bf16x8, u32x4{(unsigned)kt, (unsigned)ni, 5u, (unsigned)lane});
-#else
 #pragma unroll
             for (int mi = 0; mi < MI; ++mi) load_frag(Xs, wm * 64 + mi * 16 + li, ks, g, xf[mi]);
 #pragma unroll
             for (int ni = 0; ni < NI; ++ni) load_frag(Ws, wn * 128 + ni * 16 + li, ks, g, wf[ni]);
-#endif
 #pragma unroll
             for (int mi = 0; mi < MI; ++mi) {
-#ifndef VP_EXP_NODMA
-                if (more) stage_piece(kt + 1, (kt + 1) & 1, ks * 4 + mi);
-#endif
+                if (more && ks == my_half) {
+                    role_piece(kt + 1, (kt + 1) & 1, 2 * mi);
+                    role_piece(kt + 1, (kt + 1) & 1, 2 * mi + 1);
+                }
 #pragma unroll
                 for (int ni = 0; ni < NI; ++ni) mma(wf[ni], xf[mi], acc[mi][ni]);
             }
         }
     }
-    } else {
-    // Ping-pong schedule.  Every K-step is four phases closed by a workgroup barrier; a wave alternates
-    // L phases (fetch the 12 fragments of one 32-deep half step from LDS, issue DMAs) and C phases (its 32
-    // MFMAs on those fragments).  Waves 4..7 -- the second wave of each SIMD -- run ONE phase behind waves
-    // 0..3, so while one wave of a SIMD waits on LDS its partner owns the MFMA pipe:
-    //   phase      4kt        4kt+1      4kt+2      4kt+3
-    //   waves 0-3  L(kt,0)    C(kt,0)    L(kt,1)    C(kt,1)
-    //   waves 4-7  C(kt-1,1)  L(kt,0)    C(kt,0)    L(kt,1)
-    // Buffer (kt+1)&1 was last read in phase 4kt-1, so stage kt+1 is issued in phase 4kt (waves 0-3) /
-    // 4kt+1 (waves 4-7), waited for (vmcnt) before the barrier that closes phase 4kt+3 and first read in
-    // phase 4kt+4.  Raw s_barrier: __syncthreads() would drain the DMAs in flight at every phase.
-    // Each role gets its own straight-line loop (one branch at the top): a single loop with per-phase role
-    // tests makes hipcc shuffle the 176 live accumulator / fragment registers through scratch.
-    Frag<bf16_t> xf[MI], wf[NI];
-    auto fetch = [&](int kt, int ks) {
-        const char* Xs = smem + (kt & 1) * STAGE2;
-        const char* Ws = Xs + T2 * ROWB;
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi) load_frag(Xs, wm * 64 + mi * 16 + li, ks, g, xf[mi]);
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni) load_frag(Ws, wn * 128 + ni * 16 + li, ks, g, wf[ni]);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    };
-    auto mfmas = [&]() {
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < NI; ++ni) mma(wf[ni], xf[mi], acc[mi][ni]);
-    };
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-#ifdef VP_TIMING
-    tk1 = wall_clock64();
-#endif
-    if (wv < 4) {
-        for (int kt = 0; kt < KT; ++kt) {
-            if (kt + 1 < KT) stage(kt + 1, (kt + 1) & 1);
-            fetch(kt, 0);
-            __builtin_amdgcn_s_barrier();
-            mfmas();
-            __builtin_amdgcn_s_barrier();
-            fetch(kt, 1);
-            __builtin_amdgcn_s_barrier();
-            mfmas();
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-        }
-        __builtin_amdgcn_s_barrier();                          // phase 4 KT: the late waves' last MFMAs
-    } else {
-        __builtin_amdgcn_s_barrier();                          // phase 0: the early waves' first fetch
-        for (int kt = 0; kt < KT; ++kt) {
-            if (kt + 1 < KT) stage(kt + 1, (kt + 1) & 1);
-            fetch(kt, 0);
-            __builtin_amdgcn_s_barrier();
-            mfmas();
-            __builtin_amdgcn_s_barrier();
-            fetch(kt, 1);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            mfmas();
-            __builtin_amdgcn_s_barrier();
-        }
-    }
-    }
-    }
 #ifdef VP_TIMING
     const unsigned long long tk2 = wall_clock64();
     const unsigned long long ck2 = clock64();
-#endif
-
-#ifdef VP_TIMING
     const unsigned long long te0 = wall_clock64();
 #endif
     __syncthreads();                                           // every wave is done reading the K panels
@@ -696,14 +507,14 @@ __global__ __launch_bounds__(512) void conv_gemm256_kernel(const ConvArgs a) {
         __syncthreads();
         if (tid == 0) {
             unsigned long long* o = (unsigned long long*)a.add_in + (size_t)blockIdx.x * 8;
-            o[0] = tk0; o[1] = tk1; o[2] = tk2; o[3] = wall_clock64(); o[4] = te0; o[5] = ck2 - ck1; o[6] = te0; o[7] = (twait << 32) | tbar;
+            o[0] = tk0; o[1] = tk1; o[2] = tk2; o[3] = wall_clock64(); o[4] = te0; o[5] = ck2 - ck1; o[6] = te0; o[7] = 0;
         }
     }
 #endif
 }
 
 // ------------------------------------------------------------------------------------------------
-// Half-tile ring schedule (schedules 4 / 5).
+// Half-tile ring schedule (K256_RING).
 // A K-step is 64 wide (one 128-byte line per tile row -- a ring of 64-byte rows was measured first and fetches every
 // line twice: TCP -> TCC read requests 43.6 M vs 22.0 M per MFA launch).  Per K-step t the operands are FOUR half-tiles of
 // 128 rows x 128 B = 16 KB: XA / XB = the first / second 32 of every wave row-group's 64 positions, WA / WB = the first /
@@ -724,12 +535,10 @@ __global__ __launch_bounds__(512) void conv_gemm256_kernel(const ConvArgs a) {
 constexpr int HT = 128 * ROWB;               // one half-tile: 128 rows x 128 B
 constexpr int K_XA = 0, K_XB = 1, K_WA = 2, K_WB = 3;
 
-// PERSIST: one workgroup per CU walks the tile list with stride gridDim.x (a multiple of 8, so a workgroup stays on the
-// XCD whose run of the tile order it serves) instead of one workgroup per tile.
 // Every wave runs a phase's MFMA-only half first, then its memory half (measured against memory-half-first and against the
 // younger waves at priority 1: 314 / 326 / 322 us on the MFA GEMM).  Giving the two waves of a SIMD opposite orders needs two
 // copies of the loop: hipcc then spills fragment registers inside it -- scratch reloads wait vmcnt(0) and drain the DMA ring.
-template <int MODE, bool PERSIST>
+template <int MODE>
 __global__ __launch_bounds__(512) void conv_gemm256_ring_kernel(const ConvArgs a) {
     constexpr int MI = 4, NI = 8;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -738,7 +547,6 @@ __global__ __launch_bounds__(512) void conv_gemm256_ring_kernel(const ConvArgs a
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wv >> 1, wn = wv & 1;
     const int li = lane & 15, g = lane >> 4;
-    const int ntiles = a.tiles_m * a.tiles_n;
     constexpr unsigned OOB = 0xfffffff0u;
     const __amdgpu_buffer_rsrc_t xsrd = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.x), 0, a.x_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t wsrd = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.w), 0, a.w_bytes, 0x00020000);
@@ -751,7 +559,6 @@ __global__ __launch_bounds__(512) void conv_gemm256_ring_kernel(const ConvArgs a
     const unsigned ldxb = (unsigned)a.ldx * 2u;
     unsigned xo[2][2], wo[2][2];             // [half][piece]
     int xp[2][2];
-    int tm, m0, n0;
     // MODE_1X1 (host-checked: T_in == T_out, stride 1, no padding -- source row m for output row m): every source offset is a
     // lane part (row-in-piece x row bytes + swizzled chunk, one VGPR per operand) plus a wave-uniform part (tile, piece row,
     // K-step); rows past M / N and K-steps past K land past num_records = zeros.  Eight offset VGPRs and their selects less.
@@ -760,47 +567,36 @@ __global__ __launch_bounds__(512) void conv_gemm256_ring_kernel(const ConvArgs a
     const unsigned wl = (unsigned)srow * ldwb + cb;
     unsigned xs0 = 0, ws0 = 0;               // scalar: byte offset of the wave's first row of XA / WA in this tile
     constexpr unsigned PAST = 0xf0000000u;
-    // tile `bid` of the XCD-aware grouped order (conv_gemm_impl.h) and this wave's DMA source offsets in it
-    auto setup = [&](int bid) {
-    const int nblk = ntiles;
+    // this workgroup's tile in the XCD-aware grouped order (conv_gemm_impl.h) and this wave's DMA source offsets in it
+    const int nblk = a.tiles_m * a.tiles_n, bid = blockIdx.x;
     const int qq = nblk >> 3, rr = nblk & 7, xcd = bid & 7;
     const int swz = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
     const int gsz = a.group_m * a.tiles_n;
     const int grp = swz / gsz, rem = swz - grp * gsz;
     const int gm = min(a.group_m, a.tiles_m - grp * a.group_m);
     const int tn = rem / gm;
-    tm = grp * a.group_m + (rem - tn * gm);
-    m0 = tm * T2; n0 = tn * T2;
+    const int tm = grp * a.group_m + (rem - tn * gm);
+    const int m0 = tm * T2, n0 = tn * T2;
     if constexpr (MODE == MODE_1X1) {
         xs0 = (unsigned)(m0 + (wv >> 1) * 64 + (wv & 1) * 16) * ldxb;
         ws0 = (unsigned)(n0 + (wv >> 2) * 128 + (wv & 3) * 16) * ldwb;
-        return;
-    }
+    } else {
 #pragma unroll
-    for (int h = 0; h < 2; ++h)
+        for (int h = 0; h < 2; ++h)
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int r = wv * 16 + i * 8 + srow;                          // row of the half-tile
-            const int m = m0 + (r >> 5) * 64 + h * 32 + (r & 31);
-            const bool ok = m < a.M;
-            const int mm = ok ? m : 0;
-            const int b = mm / a.T_out;
-            const int t = mm - b * a.T_out;
-            xp[h][i] = t * a.stride - a.pad_left;
-            const unsigned ro = ok ? ((unsigned)(b * a.T_in) * (unsigned)a.ldx + (unsigned)a.xoff) * 2u : OOB;
-            if constexpr (MODE == MODE_1X1) {
-                const int traw = xp[h][i];
-                int ts = traw < 0 ? -traw : traw;
-                ts = ts >= a.T_in ? 2 * (a.T_in - 1) - ts : ts;
-                const bool inr = traw >= 0 && traw < a.T_in;
-                xo[h][i] = (ok && (inr || !zero_pad)) ? ro + (unsigned)ts * ldxb + cb : OOB;
-            } else {
-                xo[h][i] = ro;
+            for (int i = 0; i < 2; ++i) {
+                const int r = wv * 16 + i * 8 + srow;                          // row of the half-tile
+                const int m = m0 + (r >> 5) * 64 + h * 32 + (r & 31);
+                const bool ok = m < a.M;
+                const int mm = ok ? m : 0;
+                const int b = mm / a.T_out;
+                const int t = mm - b * a.T_out;
+                xp[h][i] = t * a.stride - a.pad_left;
+                xo[h][i] = ok ? ((unsigned)(b * a.T_in) * (unsigned)a.ldx + (unsigned)a.xoff) * 2u : OOB;
+                const int n = n0 + (r >> 6) * 128 + h * 64 + (r & 63);
+                wo[h][i] = n < a.N ? (unsigned)n * (unsigned)a.K * 2u + cb : OOB;
             }
-            const int n = n0 + (r >> 6) * 128 + h * 64 + (r & 63);
-            wo[h][i] = n < a.N ? (unsigned)n * (unsigned)a.K * 2u + cb : OOB;
-        }
-    };
+    }
     const int KT = a.KT;
     const int KTp = (KT + 1) & ~1;
 
@@ -823,9 +619,6 @@ __global__ __launch_bounds__(512) void conv_gemm256_ring_kernel(const ConvArgs a
             bool ok = tv && off != OOB;
             if constexpr (MODE == MODE_TAPS_GEN) ok = ok && (t * 8 + (int)(cb >> 4)) < a.KC;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(wsrd, (lds_ptr_t)dst, 16, ok ? off + kb : OOB, 0, 0, 0);
-        } else if constexpr (MODE == MODE_1X1) {
-            const unsigned off = xo[h][i];
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(xsrd, (lds_ptr_t)dst, 16, (tv && off != OOB) ? off + kb : OOB, 0, 0, 0);
         } else {
             int j;
             unsigned cbyte;
@@ -890,8 +683,7 @@ __global__ __launch_bounds__(512) void conv_gemm256_ring_kernel(const ConvArgs a
         }
     };
 
-    // prologue: the eight half-tiles of K-steps 0 and 1 in the order they are read (K-step 0 = set 0 may have been staged
-    // during the previous tile's epilogue), then the first two reads
+    // prologue: the eight half-tiles of K-steps 0 and 1 in the order they are read, then the first two reads
     constexpr int first4[4] = {K_WA, K_XA, K_XB, K_WB};
     auto stage_set = [&](int s) {
 #pragma unroll
@@ -900,12 +692,7 @@ __global__ __launch_bounds__(512) void conv_gemm256_ring_kernel(const ConvArgs a
             issue_piece(s, s, first4[q], 1);
         }
     };
-    int bid = blockIdx.x;
-    if (bid < ntiles) {
-        setup(bid);
-        stage_set(0);
-    }
-    while (bid < ntiles) {
+    stage_set(0);
 #ifdef VP_TIMING
     const unsigned long long tk0 = wall_clock64();
 #endif
@@ -1005,11 +792,8 @@ __global__ __launch_bounds__(512) void conv_gemm256_ring_kernel(const ConvArgs a
     const unsigned long long ck2 = clock64();
     const unsigned long long te0 = tk2;
 #endif
-    const int ctm = tm, cm0 = m0, cn0 = n0;
-    const int nbid = PERSIST ? bid + (int)gridDim.x : ntiles;
     __syncthreads();                                           // every wave is done reading the ring
-    static_assert(!PERSIST, "the resident-workgroup variant (round 2, schedule 5: slower than one workgroup per tile) is no longer built");
-    epilogue256<8, bf16_t>(a, acc, smem, tid, ctm, cm0, cn0);
+    epilogue256<8, bf16_t>(a, acc, smem, tid, tm, m0, n0);
 #ifdef VP_TIMING
     if (!a.aux && a.add_in) {
         __syncthreads();
@@ -1019,12 +803,10 @@ __global__ __launch_bounds__(512) void conv_gemm256_ring_kernel(const ConvArgs a
         }
     }
 #endif
-    bid = nbid;
-    }
 }
 
 // ------------------------------------------------------------------------------------------------
-// Two workgroups per CU (schedule 6): the half-tile ring on a 128-position x 256-channel tile, 4 waves, 80 KB of LDS.
+// Two workgroups per CU (K128X256_RING): the half-tile ring on a 128-position x 256-channel tile, 4 waves, 80 KB of LDS.
 // Why: with one 8-wave workgroup per CU a tile's prologue (first HBM round trip), K-loop and epilogue (128 KB of stores when
 // every CU of the chip stores at once) run back to back and nothing overlaps them -- for a K = 512 layer they are 40 % of the
 // tile -- and 596 full tiles on 256 CUs are 2.33 rounds.  Here each SIMD hosts one wave of EACH of two independent
@@ -1269,61 +1051,50 @@ int launch256_ring(vp_ctx* ctx, const ConvArgs& a, hipStream_t st) {
     static bool attr_dev[64] = {};                    // the attribute is per DEVICE (a process may drive several GPUs)
     bool& attr_set = attr_dev[ctx->device & 63];
     if (!attr_set) {
-        VP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv_gemm256_ring_kernel<MODE, false>),
+        VP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv_gemm256_ring_kernel<MODE>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, smem));
         attr_set = true;
     }
-    hipLaunchKernelGGL((conv_gemm256_ring_kernel<MODE, false>), dim3(a.tiles_m * a.tiles_n), dim3(512), smem, st, a);
+    hipLaunchKernelGGL((conv_gemm256_ring_kernel<MODE>), dim3(a.tiles_m * a.tiles_n), dim3(512), smem, st, a);
     VP_LAUNCH_CHECK(ctx, "conv_gemm256_ring");
     return VP_OK;
 }
 
-template <int MODE, int SCHED>
+template <int MODE>
 int launch256(vp_ctx* ctx, const ConvArgs& a, hipStream_t st) {
     constexpr int smem = 8 * 64 * 272 + 2 * 4 * 2 * T2 * 4;      // output slabs + column-sum partials (> the K panels)
     static bool attr_dev[64] = {};                    // the attribute is per DEVICE (a process may drive several GPUs)
     bool& attr_set = attr_dev[ctx->device & 63];
     if (!attr_set) {
-        VP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv_gemm256_kernel<MODE, SCHED>),
+        VP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv_gemm256_kernel<MODE>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, smem));
         attr_set = true;
     }
-    hipLaunchKernelGGL((conv_gemm256_kernel<MODE, SCHED>), dim3(a.tiles_m * a.tiles_n), dim3(512), smem, st, a);
+    hipLaunchKernelGGL((conv_gemm256_kernel<MODE>), dim3(a.tiles_m * a.tiles_n), dim3(512), smem, st, a);
     VP_LAUNCH_CHECK(ctx, "conv_gemm256");
     return VP_OK;
 }
 
 }  // namespace
 
-// split precision: x and w hl32 tensors (1x1 layer, source row m for output row m), hl32 or f32 out; args as for schedule 6
-int vp_conv_launch_ring_x3(vp_ctx* ctx, const void* args, int out_f32, hipStream_t st) {
-    const ConvArgs& a = *static_cast<const ConvArgs*>(args);
+// split precision: x and w hl32 tensors (1x1 layer, source row m for output row m), hl32 or f32 out; args as for K128X256_RING
+int vp_conv_launch_ring_x3(vp_ctx* ctx, const ConvArgs& a, int out_f32, hipStream_t st) {
     return out_f32 ? launch128x256_ring<float, true>(ctx, a, st) : launch128x256_ring<hl_t, true>(ctx, a, st);
 }
 
-// args: ConvArgs with tiles_m / tiles_n / group_m already set for 256-wide tiles
-// out_f32: bf16 operands, f32 output (the training engine's data-gradient GEMMs) -- schedule 6 only
-int vp_conv_launch256_bf16(vp_ctx* ctx, const void* args, int mode, int sched, int out_f32, hipStream_t st) {
-    const ConvArgs& a = *static_cast<const ConvArgs*>(args);
-    if (out_f32 && (sched != 5 || mode != MODE_1X1)) VP_FAIL(ctx, VP_EUNSUP, "conv256: f32 output needs the 128 x 256 schedule on a 1x1 layer");
-    if (sched == 0) {
-        if (mode == MODE_1X1) return launch256<MODE_1X1, 0>(ctx, a, st);
-        if (mode == MODE_TAPS) return launch256<MODE_TAPS, 0>(ctx, a, st);
-    } else if (sched == 1) {
-        if (mode == MODE_1X1) return launch256<MODE_1X1, 1>(ctx, a, st);
-        if (mode == MODE_TAPS) return launch256<MODE_TAPS, 1>(ctx, a, st);
-    } else if (sched == 5) {
-        // two workgroups per CU on 128 x 256 tiles (1x1 layers); args carry tiles_m in 128-row units
-        if (mode == MODE_1X1) return out_f32 ? launch128x256_ring<float, false>(ctx, a, st) : launch128x256_ring<bf16_t, false>(ctx, a, st);
-    } else if (sched == 3 || sched == 4) {
-        // half-tile ring: one workgroup per tile (3) or resident workgroups (4)
-        if (mode == MODE_1X1) return launch256_ring<MODE_1X1>(ctx, a, st);      // (4 = resident workgroups: no longer built, runs as 3)
-        // tapped convs stay on the two-stage schedule: their per-piece tap / reflect arithmetic pushes the ring loop past
-        // 256 VGPRs (scratch reloads inside the loop wait vmcnt(0) and drain the ring)
-        if (mode == MODE_TAPS) return a.Cin % 64 == 0 ? launch256<MODE_TAPS, 2>(ctx, a, st) : launch256<MODE_TAPS_GEN, 2>(ctx, a, st);
-    } else {
-        if (mode == MODE_1X1) return launch256<MODE_1X1, 2>(ctx, a, st);
-        if (mode == MODE_TAPS) return a.Cin % 64 == 0 ? launch256<MODE_TAPS, 2>(ctx, a, st) : launch256<MODE_TAPS_GEN, 2>(ctx, a, st);
+// bf16 operands on the kernel family and mode conv_plan() picked (conv_gemm.hip); a carries tiles_m / tiles_n / group_m in units of
+// that family's tile.  out_f32: f32 output (the training engine's data-gradient GEMMs), K128X256_RING only.
+// The ring kernels are built for 1x1 layers: the per-piece tap / reflect arithmetic of a tapped conv pushes the ring loop past
+// 256 VGPRs (scratch reloads inside the loop wait vmcnt(0) and drain the ring), so those stay on the two-stage kernel.
+int vp_conv_launch256_bf16(vp_ctx* ctx, const ConvArgs& a, ConvKernel kernel, int mode, int out_f32, hipStream_t st) {
+    if (out_f32 && kernel != K128X256_RING) VP_FAIL(ctx, VP_EUNSUP, "conv256: f32 output needs the 128 x 256 ring");
+    if (kernel == K128X256_RING && mode == MODE_1X1)
+        return out_f32 ? launch128x256_ring<float, false>(ctx, a, st) : launch128x256_ring<bf16_t, false>(ctx, a, st);
+    if (kernel == K256_RING && mode == MODE_1X1) return launch256_ring<MODE_1X1>(ctx, a, st);
+    if (kernel == K256_TWO_STAGE) {
+        if (mode == MODE_1X1) return launch256<MODE_1X1>(ctx, a, st);
+        if (mode == MODE_TAPS) return launch256<MODE_TAPS>(ctx, a, st);
+        if (mode == MODE_TAPS_GEN) return launch256<MODE_TAPS_GEN>(ctx, a, st);
     }
-    VP_FAIL(ctx, VP_EUNSUP, "conv256: mode %d not built", mode);
+    VP_FAIL(ctx, VP_EUNSUP, "conv256: kernel %d / mode %d not built", (int)kernel, mode);
 }

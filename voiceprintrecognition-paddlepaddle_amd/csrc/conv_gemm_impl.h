@@ -7,17 +7,12 @@
 
 #include <type_traits>
 
-namespace {
-
-constexpr int BM = VP_CONV_BM;
-constexpr int ROWB = 128;        // bytes of K per tile row per stage
-constexpr int NSEG_MAX = 8;
-
 // loader / prologue flavour of an instantiation
 constexpr int MODE_TAPS = 0;     // 1-D conv, KW taps along time (reflect / zero / none)
 constexpr int MODE_1X1 = 1;      // KW == 1: source row fixed, address hoisted out of the K loop
 constexpr int MODE_2D = 2;       // 2-D conv over (time, freq), zero padding, stride on freq
 constexpr int MODE_1X1_PRO = 3;  // 1x1 with BN-affine + ReLU applied to the INPUT channels while staging
+constexpr int MODE_TAPS_GEN = 4; // tapped 1-D conv with Cin % 64 != 0: a K-step may straddle taps (conv_gemm256.hip, two-stage kernel only)
 
 struct ConvArgs {
     const void* x; const void* w;
@@ -33,6 +28,33 @@ struct ConvArgs {
     int gate_len, gate_nseg;
     int tiles_m, tiles_n, nseg, group_m;
 };
+
+// kernel family of a launch (the public VP_CONV_K* ids of vpmi.h), picked by conv_plan() in conv_gemm.hip
+enum ConvKernel {
+    K128 = VP_CONV_K128,                        // conv_gemm_kernel below: 128-row tiles, 128 / 64 / 32 columns
+    K256_TWO_STAGE = VP_CONV_K256_TWO_STAGE,    // conv_gemm256.hip: 256 x 256 tiles, role-split DMA into two 64 KB stages
+    K256_RING = VP_CONV_K256_RING,              // conv_gemm256.hip: 256 x 256 tiles, half-tile ring
+    K128X256_RING = VP_CONV_K128X256_RING,      // conv_gemm256.hip: 128 x 256 tiles, two workgroups per CU (bf16 or split precision)
+};
+
+// the launchers vp_conv1d_fwd switches over: K128 per (input, output) type pair -- bn = tile columns -- and the wide tiles, whose
+// ConvArgs carry tiles_m / tiles_n / group_m in units of their own tile
+int vp_conv_launch_bf16_bf16(vp_ctx* ctx, const ConvArgs& a, int bn, int mode, hipStream_t st);
+int vp_conv_launch_bf16_f32(vp_ctx* ctx, const ConvArgs& a, int bn, int mode, hipStream_t st);
+int vp_conv_launch_f32_f32(vp_ctx* ctx, const ConvArgs& a, int bn, int mode, hipStream_t st);
+int vp_conv_launch_amp_f32(vp_ctx* ctx, const ConvArgs& a, int bn, int mode, hipStream_t st);
+int vp_conv_launch_x3_f32(vp_ctx* ctx, const ConvArgs& a, int bn, int mode, hipStream_t st);
+int vp_conv_launch_x3w_f32(vp_ctx* ctx, const ConvArgs& a, int bn, int mode, hipStream_t st);
+int vp_conv_launch_x3_hl(vp_ctx* ctx, const ConvArgs& a, int bn, int mode, hipStream_t st);
+int vp_conv_launch_hl_hl(vp_ctx* ctx, const ConvArgs& a, int bn, int mode, hipStream_t st);
+int vp_conv_launch_ring_x3(vp_ctx* ctx, const ConvArgs& a, int out_f32, hipStream_t st);
+int vp_conv_launch256_bf16(vp_ctx* ctx, const ConvArgs& a, ConvKernel kernel, int mode, int out_f32, hipStream_t st);
+
+namespace {
+
+constexpr int BM = VP_CONV_BM;
+constexpr int ROWB = 128;        // bytes of K per tile row per stage
+constexpr int NSEG_MAX = 8;
 
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 

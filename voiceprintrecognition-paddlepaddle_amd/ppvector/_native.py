@@ -20,6 +20,7 @@ VP_PAD_NONE, VP_PAD_REFLECT, VP_PAD_ZERO = 0, 1, 2
 VP_ACT_NONE, VP_ACT_RELU, VP_ACT_SIGMOID, VP_ACT_TANH, VP_ACT_HARDTANH20, VP_ACT_SILU = 0, 1, 2, 3, 4, 5
 VP_LOSS_AAM, VP_LOSS_AM, VP_LOSS_ARM, VP_LOSS_CE, VP_LOSS_SUBCENTER = 0, 1, 2, 3, 4
 VP_MAX_SE_BLOCKS, VP_MAX_RES2 = 8, 15
+VP_CONV_K128, VP_CONV_K256_TWO_STAGE, VP_CONV_K256_RING, VP_CONV_K128X256_RING = 0, 1, 2, 3
 
 c_void_p, c_int, c_float, c_size_t = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 
@@ -235,6 +236,7 @@ _PROTOS = {
     'vp_conv1d_tiles_m': (c_int, [c_int, c_int]),
     'vp_conv1d_nseg': (c_int, [c_int]),
     'vp_conv1d_fwd': (c_int, [c_void_p, C.POINTER(Conv1dDesc), c_void_p]),
+    'vp_conv1d_plan': (c_int, [C.POINTER(Conv1dDesc)] + [C.POINTER(c_int)] * 6),
     'vp_moments_finalize': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int,
                                     c_void_p, c_void_p]),
     'vp_dense_f32': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int,
