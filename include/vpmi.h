@@ -454,6 +454,27 @@ int vp_wave_batch_f32(vp_ctx* ctx, const float* const* srcs, const int32_t* lens
  * new_lens[b] = int(lens[b] / rate)).  srcs / dsts: DEVICE arrays of B device pointers. */
 int vp_speed_perturb_f32(vp_ctx* ctx, const float* const* srcs, const int32_t* lens, const int32_t* new_lens,
                          float* const* dsts, int B, int max_new_len, vp_stream stream);
+/* Noise perturbation (NoisePerturbAugmentor -> AudioSegment.add_noise, call site data_utils/reader.py:159-160;
+ * configs/augmentation.yml:17-26; yeaudio is third party, restated): dsts[b][i] = srcs[b][i] + g * noises[b][(noise_starts[b] + i)
+ * mod noise_lens[b]], g = 10^(min(rms_dB(src) - rms_dB(noise) - snr_db[b], 300) / 20), rms_dB(v) = 10 log10(max(mean v^2, 1e-20)).
+ * The noise level is measured over the file wrap-padded to lens[b] samples when it is shorter than the utterance, over the
+ * whole file otherwise; not clipped.  The host draws the file, snr_db and the start (NULL = 0) and has decoded and resampled
+ * the noise.  srcs / noises / dsts: DEVICE arrays of B device pointers; dsts[b] holds lens[b] samples and must not alias
+ * srcs[b].  A row with lens[b] or noise_lens[b] outside [1, 2^30] is left alone. */
+int vp_noise_mix_f32(vp_ctx* ctx, const float* const* srcs, const int32_t* lens, const float* const* noises,
+                     const int32_t* noise_lens, const int32_t* noise_starts, const float* snr_db, float* const* dsts, int B,
+                     vp_stream stream);
+/* Reverberation (ReverbPerturbAugmentor -> AudioSegment.reverb, call site data_utils/reader.py:161-162;
+ * configs/augmentation.yml:28-33; yeaudio is third party, restated): dsts[b] = convolve(srcs[b], rirs[b], 'full') cut to
+ * lens[b] samples.  rirs[b] is the impulse response already scaled to unit energy by the host (rir / sqrt(sum rir^2)).
+ * Uniformly partitioned overlap-save FFT convolution, partition 2048, 4096-point f32 transforms, partitions summed in
+ * ascending order in f32.  max_len >= every lens[b] and max_rir_len >= every rir_lens[b] size the launch and the workspace
+ * (longer rows are cut to them).  Workspace: B * (ceil(max_len / 2048) + ceil(max_rir_len / 2048)) * 2056 * 8 bytes; every
+ * element read was written by the same call.  srcs / rirs / dsts: DEVICE arrays of B device pointers; dsts[b] must not
+ * alias srcs[b].  A row with lens[b] <= 0 or rir_lens[b] <= 0 is left alone. */
+size_t vp_reverb_workspace_bytes(int B, int max_len, int max_rir_len);
+int vp_reverb_f32(vp_ctx* ctx, const float* const* srcs, const int32_t* lens, const float* const* rirs, const int32_t* rir_lens,
+                  float* const* dsts, int B, int max_len, int max_rir_len, void* ws, size_t ws_bytes, vp_stream stream);
 
 /* ------------------------------------------------------------------------------------------------
  * ResNetSE backbone forward, eval mode -- replaces ResNetSE.forward (models/resnet_se.py:121-139) with

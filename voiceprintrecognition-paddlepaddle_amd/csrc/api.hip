@@ -24,6 +24,7 @@ void vp_destroy(vp_ctx* ctx) {
     if (!ctx) return;
     vp_fbank_release_tables(ctx);
     vp_mel_release_tables(ctx);
+    vp_reverb_release_tables(ctx);
     if (ctx->grid_bar_own) (void)hipFree(ctx->grid_bar_own);
     free(ctx);
 }

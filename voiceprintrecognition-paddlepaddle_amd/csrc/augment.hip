@@ -6,6 +6,8 @@
 // feature -- or zero) is restated in oracle/augment.py.  The random draws stay on the host (same Python `random`
 // call sequence as the restatement); this kernel applies the drawn masks to the whole batch in place.
 // Collation: collate_fn (ppvector/data_utils/collate_fn.py:5-23) = zero-pad every (T_i, F) feature to T_max.
+// Waveform side: dB normalisation + crop + pad, speed perturbation, noise perturbation (reader.py:97-101,155-160); the reverb
+// convolution has its own file (reverb.hip).
 #include "common.h"
 
 namespace {
@@ -116,6 +118,69 @@ __global__ __launch_bounds__(256) void speed_perturb_kernel(SpeedArgs a) {
     }
 }
 
+// Noise perturbation (yeaudio NoisePerturbAugmentor -> AudioSegment.add_noise, third party, restated [3P-memory]): one workgroup per
+// utterance -- of 1024 threads with four independent partial sums each: a single workgroup streams ~1 MB here and is bound by the
+// loads it keeps in flight; two fixed-order sums of squares as in wave_batch_kernel (the utterance; the noise -- over its wrap-padded n samples when
+// the file is shorter than the utterance, over the WHOLE file otherwise, as yeaudio measures it before it cuts the segment), then
+// dst[i] = x[i] + g * noise[(start + i) mod Ln].  g = 10^(min(rms_dB(x) - rms_dB(noise) - snr_dB, 300) / 20) with rms_dB(v) =
+// 10 log10(max(mean v^2, 1e-20)), evaluated as min(sqrt(msx / msn) * 10^(-snr_dB / 20), 1e15): the same number without the
+// rounding of a ~200 dB intermediate when the utterance is silent.
+struct NoiseArgs {
+    const float* const* src; const float* const* noise; float* const* dst;
+    const int* lens; const int* noise_lens; const int* starts; const float* snr_db;
+};
+
+constexpr int NM_THREADS = 1024;
+
+// sum over the workgroup in a fixed order: wave shuffles, then the 16 wave sums one after the other
+__device__ __forceinline__ float noise_block_sum(float v, float* sm, int tid) {
+    v = vp_wave_sum(v);
+    if ((tid & 63) == 0) sm[tid >> 6] = v;
+    __syncthreads();
+    float r = 0.f;
+#pragma unroll
+    for (int w = 0; w < NM_THREADS / 64; ++w) r += sm[w];
+    __syncthreads();
+    return r;
+}
+
+// sum of v[idx(i)]^2 over i = tid, tid + T, ... < m: four strided partial sums per thread, combined in a fixed order
+template <typename Idx>
+__device__ __forceinline__ float noise_sumsq(const float* v, int m, int tid, Idx idx) {
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    int i = tid;
+    for (; i < m - 3 * NM_THREADS; i += 4 * NM_THREADS) {
+        const float a0 = v[idx(i)], a1 = v[idx(i + NM_THREADS)], a2 = v[idx(i + 2 * NM_THREADS)], a3 = v[idx(i + 3 * NM_THREADS)];
+        s0 += a0 * a0; s1 += a1 * a1; s2 += a2 * a2; s3 += a3 * a3;
+    }
+    for (; i < m; i += NM_THREADS) { const float a0 = v[idx(i)]; s0 += a0 * a0; }
+    return (s0 + s1) + (s2 + s3);
+}
+
+__global__ __launch_bounds__(NM_THREADS) void noise_mix_kernel(NoiseArgs a) {
+    __shared__ float sm[NM_THREADS / 64];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int n = a.lens[b], Ln = a.noise_lens[b];
+    if (n <= 0 || Ln <= 0 || n > (1 << 30) || Ln > (1 << 30)) return;      // uniform per workgroup; the bound keeps every index sum in int
+    const float* __restrict__ x = a.src[b];
+    const float* __restrict__ nz = a.noise[b];
+    float* __restrict__ o = a.dst[b];                           // never the source (vpmi.h)
+    const float sx = noise_block_sum(noise_sumsq(x, n, tid, [](int i) { return i; }), sm, tid);
+    const int m = Ln < n ? n : Ln;                               // samples the noise level is measured over
+    const float sn = noise_block_sum(noise_sumsq(nz, m, tid, [Ln](int i) { return i < Ln ? i : i % Ln; }), sm, tid);
+    const float msx = fmaxf(sx / (float)n, 1e-20f), msn = fmaxf(sn / (float)m, 1e-20f);
+    const float gain = fminf(sqrtf(msx / msn) * exp10f(-0.05f * a.snr_db[b]), 1e15f);
+    int st = a.starts ? a.starts[b] : 0;
+    st = st < 0 ? 0 : (st >= Ln ? Ln - 1 : st);
+    const unsigned s = (unsigned)st, L = (unsigned)Ln;
+#pragma unroll 4
+    for (int i = tid; i < n; i += NM_THREADS) {
+        unsigned j = s + (unsigned)i;
+        if (j >= L) j %= L;
+        o[i] = x[i] + gain * nz[j];
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -176,6 +241,16 @@ int vp_speed_perturb_f32(vp_ctx* ctx, const float* const* srcs, const int32_t* l
     SpeedArgs a{srcs, lens, new_lens, dsts};
     hipLaunchKernelGGL(speed_perturb_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, a);
     VP_LAUNCH_CHECK(ctx, "speed_perturb");
+    return VP_OK;
+}
+
+int vp_noise_mix_f32(vp_ctx* ctx, const float* const* srcs, const int32_t* lens, const float* const* noises, const int32_t* noise_lens,
+                     const int32_t* noise_starts, const float* snr_db, float* const* dsts, int B, vp_stream stream) {
+    if (!ctx || !srcs || !lens || !noises || !noise_lens || !snr_db || !dsts || B <= 0 || B > 65535)
+        VP_FAIL(ctx, VP_EINVAL, "noise_mix: bad arguments");
+    NoiseArgs a{srcs, noises, dsts, lens, noise_lens, noise_starts, snr_db};
+    hipLaunchKernelGGL(noise_mix_kernel, dim3(B), dim3(NM_THREADS), 0, (hipStream_t)stream, a);
+    VP_LAUNCH_CHECK(ctx, "noise_mix");
     return VP_OK;
 }
 

@@ -29,6 +29,8 @@ struct vp_ctx {
     int* ms_mel_start;
     int* ms_mel_bin0;
     float* ms_mel_w;
+    // twiddles of the reverberation FFT (reverb.hip; built on first use)
+    float2* rv_twiddle;   // [4096]
     // device margin table of the margin-softmax losses (vp_set_margin_table): [margin, cos m, sin m, cos(pi - m), 1 + cos(pi - m)]
     const float* margin_table;
     // counters of the in-kernel grid barrier (res2_train.hip): eight arrival counters 32 words apart, [256] departures, [257] bail-out
@@ -165,6 +167,7 @@ int vp_cam_block_bf16(vp_ctx* ctx, const vp_cam_layer* layers, int n_layers, voi
 // kernels' host launchers (defined in the .hip files)
 int vp_fbank_release_tables(vp_ctx* ctx);
 int vp_mel_release_tables(vp_ctx* ctx);
+int vp_reverb_release_tables(vp_ctx* ctx);
 
 // tanh for an epilogue whose result is stored as TO: bf16 outputs (8 mantissa bits) take 1 - 2 / (2^(2 x log2 e) + 1) on the
 // hardware exp2 / rcp (5 instructions, |error| ~1e-7); f32 outputs keep tanhf (~40 instructions: the parity instrument).

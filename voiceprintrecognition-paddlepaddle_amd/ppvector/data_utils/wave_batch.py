@@ -2,6 +2,7 @@
 of the featurizer (ppvector/data_utils/reader.py:97-101: decibel normalisation, crop to max_duration) plus the zero
 padding of predict_batch (ppvector/predict.py:246-254), as one launch over the whole batch (csrc/augment.hip
 wave_batch_kernel).  Decoding / resampling stay on the host; this takes the decoded utterances already on the device."""
+import numpy as np
 import torch
 
 from ppvector import _native as N
@@ -64,6 +65,101 @@ def speed_perturb(waves, rates):
     ctx = N.ctx(dev)
     N.check(N.lib().vp_speed_perturb_f32(ctx, sp.data_ptr(), ld.data_ptr(), nd.data_ptr(), dp.data_ptr(), len(idx), max(new_lens),
                                          N.stream_ptr()), ctx)
+    for b, w in zip(idx, dst):
+        out[b] = w
+    return out
+
+
+def _selected(name, waves, others):
+    """Shared front of noise_perturb / reverb_perturb: GPU checks, the selected rows, their flattened f32 sources and partners."""
+    waves = [torch.as_tensor(w) for w in waves]
+    if not waves or not all(w.is_cuda for w in waves):
+        raise N.VpmiError(f'{name} takes GPU waveforms: the engine has no CPU fallback')
+    if len(others) != len(waves):
+        raise ValueError(f'{name}: {len(others)} entries for {len(waves)} utterances')
+    idx = [b for b, o in enumerate(others) if o is not None]
+    oth = [torch.as_tensor(others[b]) for b in idx]
+    if not all(o.is_cuda for o in oth):
+        raise N.VpmiError(f'{name} takes GPU noise / impulse-response tensors: the engine has no CPU fallback')
+    src = [waves[b].reshape(-1).contiguous().float() for b in idx]
+    oth = [o.reshape(-1).contiguous().float() for o in oth]
+    if any(w.numel() == 0 for w in src) or any(o.numel() == 0 for o in oth):
+        raise ValueError(f'{name}: empty utterance or empty partner signal')
+    return waves, idx, src, oth
+
+
+def _ragged_empty(lens, dev):
+    """New f32 rows of the given lengths as views of ONE allocation (16-byte aligned starts), like the trainer's upload."""
+    offs = np.concatenate(([0], np.cumsum([(n + 3) // 4 * 4 for n in lens]))).tolist()
+    buf = torch.empty(max(offs[-1], 1), dtype=torch.float32, device=dev)
+    return [buf[o:o + n] for o, n in zip(offs[:-1], lens)]
+
+
+def _device_tables(dev, ptr_rows, int_rows, float_rows=()):
+    """The launch's per-utterance tables -- rows of device pointers, of int32 and of float32, k entries each -- through ONE
+    host-to-device copy.  Returns (buffer to keep alive until the launch, [device address of each row, in the order given])."""
+    k = len(ptr_rows[0])
+    host = np.empty((2 * len(ptr_rows) + len(int_rows) + len(float_rows)) * k, dtype=np.int32)
+    a, b = 2 * len(ptr_rows) * k, (2 * len(ptr_rows) + len(int_rows)) * k
+    host[:a].view(np.int64)[:] = np.asarray(ptr_rows, dtype=np.int64).ravel()
+    host[a:b] = np.asarray(int_rows, dtype=np.int32).ravel()
+    if float_rows:
+        host[b:].view(np.float32)[:] = np.asarray(float_rows, dtype=np.float32).ravel()
+    d = torch.from_numpy(host).to(dev)
+    base = d.data_ptr()
+    return d, [base + 8 * k * r for r in range(len(ptr_rows))] + [base + 4 * a + 4 * k * r for r in range(len(int_rows) + len(float_rows))]
+
+
+def noise_perturb(waves, noises, snrs_dB, noise_starts):
+    """Noise perturbation of a ragged batch on the GPU (NoisePerturbAugmentor -> AudioSegment.add_noise, reader.py:159-160).  yeaudio
+    is third party and not installed: restated from its published behaviour [3P-memory], PARITY UNPINNED.  For utterance x (n
+    samples, after the speed change) and the decoded noise file (Ln samples, first channel, at the dataset's rate):
+        Ln <  n: the noise is wrap-padded to n samples and used whole (start 0), its level measured over those n samples;
+        Ln >= n: the segment [start, start + n) is used, its level measured over the WHOLE file (yeaudio measures before it cuts);
+        e[i] = noise[(start + i) mod Ln];  rms_dB(v) = 10 log10(max(mean v^2, 1e-20));
+        out[i] = x[i] + 10^(min(rms_dB(x) - rms_dB(noise) - snr_dB, 300) / 20) * e[i], not clipped.
+    waves: list of 1-D float GPU tensors; noises[b]: 1-D float GPU tensor, or None = not selected (snrs_dB[b] / noise_starts[b] are then
+    ignored).  Returns a list: an unselected row is the SAME tensor object, a selected one a new tensor of the same length."""
+    waves, idx, src, nz = _selected('noise_perturb', waves, noises)
+    out = list(waves)
+    if not idx:
+        return out
+    dev = src[0].device
+    lens, nlens = [int(w.numel()) for w in src], [int(z.numel()) for z in nz]
+    dst = _ragged_empty(lens, dev)
+    keep, (sp, zp, dp, ld, zd, sd, snr) = _device_tables(
+        dev, [[w.data_ptr() for w in src], [z.data_ptr() for z in nz], [w.data_ptr() for w in dst]],
+        [lens, nlens, [int(noise_starts[b]) for b in idx]], [[float(snrs_dB[b]) for b in idx]])
+    ctx = N.ctx(dev)
+    N.check(N.lib().vp_noise_mix_f32(ctx, sp, ld, zp, zd, sd, snr, dp, len(idx), N.stream_ptr()), ctx)
+    for b, w in zip(idx, dst):
+        out[b] = w
+    return out
+
+
+_reverb_ws = N.Workspace()
+
+
+def reverb_perturb(waves, rirs):
+    """Reverberation of a ragged batch on the GPU (ReverbPerturbAugmentor -> AudioSegment.reverb, reader.py:161-162).  yeaudio is third
+    party and not installed: restated from its published behaviour [3P-memory], PARITY UNPINNED: out = convolve(x, h, 'full')[:n] with
+    h = rir / sqrt(sum rir^2).  rirs[b] is h ALREADY scaled to unit energy (the reader does it in float64 when it decodes the file;
+    an all-zero file is never selected), or None = not selected.  csrc/reverb.hip: partitioned overlap-save FFT convolution.
+    waves: list of 1-D float GPU tensors.  Returns a list: an unselected row is the SAME tensor object, a selected one a new tensor
+    of the same length."""
+    waves, idx, src, hs = _selected('reverb_perturb', waves, rirs)
+    out = list(waves)
+    if not idx:
+        return out
+    dev = src[0].device
+    lens, hlens = [int(w.numel()) for w in src], [int(h.numel()) for h in hs]
+    dst = _ragged_empty(lens, dev)
+    keep, (sp, hp, dp, ld, hd) = _device_tables(dev, [[w.data_ptr() for w in src], [h.data_ptr() for h in hs], [w.data_ptr() for w in dst]],
+                                                [lens, hlens])
+    need = int(N.lib().vp_reverb_workspace_bytes(len(idx), max(lens), max(hlens)))
+    ws = _reverb_ws.get(need, dev)
+    ctx = N.ctx(dev)
+    N.check(N.lib().vp_reverb_f32(ctx, sp, ld, hp, hd, dp, len(idx), max(lens), max(hlens), ws.data_ptr(), ws.numel(), N.stream_ptr()), ctx)
     for b, w in zip(idx, dst):
         out[b] = w
     return out

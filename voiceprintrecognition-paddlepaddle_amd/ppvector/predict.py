@@ -42,7 +42,8 @@ class AudioSegment:
         self.samples, self.sample_rate = samples, int(sample_rate)
 
     @classmethod
-    def from_file(cls, f):
+    def from_file(cls, f, channel=None):
+        """channel: keep that one channel of a multi-channel file (None = the mean of all)."""
         with wave.open(f, 'rb') as w:
             n, ch, sw, sr = w.getnframes(), w.getnchannels(), w.getsampwidth(), w.getframerate()
             raw = w.readframes(n)
@@ -52,7 +53,8 @@ class AudioSegment:
         x = np.frombuffer(raw, dtype=dt)
         if sw == 1:
             x = (x.astype(np.int16) - 128).astype(np.int8)
-        return cls(x.reshape(-1, ch), sr)
+        x = x.reshape(-1, ch)
+        return cls(x if channel is None else x[:, channel], sr)
 
     @classmethod
     def from_bytes(cls, b):

@@ -5,7 +5,8 @@
 What moved: the reference builds features one utterance at a time on CPU DataLoader workers (reader.py:72-109) and feeds
 (B, T, F) tensors to the device; here worker THREADS only decode audio, and one step is
 
-    decoded waves --H2D--> speed_perturb -> assemble_waves (dB normalise, crop, pad: 1 launch) -> AudioFeaturizer (Fbank / Mel + CMN)
+    decoded waves --H2D--> speed_perturb -> noise_perturb -> reverb_perturb -> assemble_waves (dB normalise, crop, pad: 1 launch)
+      -> AudioFeaturizer (Fbank / Mel + CMN)
       -> SpecAugmentor.batch -> nn.Sequential(backbone, classifier) train-mode forward -> criterion -> backward
       -> bucketed gradient all-reduce over RCCL (one process per GPU, torch.distributed) -> flat Adam step
 
@@ -31,7 +32,7 @@ from torch import nn
 
 from ppvector.data_utils.featurizer import AudioFeaturizer
 from ppvector.data_utils.reader import PPVectorDataset
-from ppvector.data_utils.wave_batch import assemble_waves, speed_perturb
+from ppvector.data_utils.wave_batch import assemble_waves, noise_perturb, reverb_perturb, speed_perturb
 from ppvector.loss import build_loss
 from ppvector.metric.metrics import evaluate_trials
 from ppvector.models import build_model
@@ -152,6 +153,16 @@ class PPVectorTrainer(object):
             return feats, labels
         waves = self._upload([it['samples'] for it in items])
         waves = speed_perturb(waves, [it.get('speed', 1.0) for it in items])
+        # noise, then reverb, on the utterances the reader selected (train mode only: eval / extract_feature items carry no such keys),
+        # in the reference's order (reader.py:159-162) and in front of the normalisation, which must see the augmented signal's level
+        noises, rirs = [it.get('noise') for it in items], [it.get('rir') for it in items]
+        picked = [a for a in noises + rirs if a is not None]
+        if picked:
+            dev = iter(self._upload(picked))                    # a second pass through the pinned buffer: one more copy
+            noises = [None if a is None else next(dev) for a in noises]
+            rirs = [None if a is None else next(dev) for a in rirs]
+            waves = noise_perturb(waves, noises, [it.get('snr_dB', 0.0) for it in items], [it.get('noise_start', 0) for it in items])
+            waves = reverb_perturb(waves, rirs)
         longest = max(min(int(w.numel()) - int(it['start']), dataset.max_samples) if dataset.mode != 'extract_feature'
                       else int(w.numel()) for w, it in zip(waves, items))
         batch, _, n_valid = assemble_waves(waves, max_len=longest, starts=[it['start'] for it in items],
