@@ -122,6 +122,19 @@ int vp_melspec_cmn_f32(vp_ctx* ctx, const float* wav, const float* lens_ratio, i
                        const vp_mel_opts* o, float* out, void* out_bf16, void* ws, size_t ws_bytes,
                        vp_stream stream);
 
+/* Ragged batch of the mel family, the training loader's semantics -- replaces the per-utterance feat_fun call of
+ * data_utils/reader.py:102-103 followed by collate_fn's zero padding (collate_fn.py:5-23) with one launch.  wav (B, L) holds
+ * utterance b in its first n_b = min(n_samples[b], L) samples; T = vp_mel_num_frames(o, L); the workspace is
+ * vp_mel_workspace_bytes(o, B, L).  An utterance with n_b > n_fft/2 has T_b = 1 + n_b / hop_length frames, each the centred
+ * frame of THAT utterance alone (reflection folds at n_b, not at L), mean-normalised over its own T_b frames; one with
+ * n_b <= n_fft/2 cannot be reflect-padded and has 0 frames (defined: nothing is read out of bounds, no error).  Rows
+ * t >= T_b of out and out_bf16 are zero; n_frames[b] = T_b is written for the caller (collate_fn's input_lens).  No sample
+ * outside row b's first n_b is used by a value that is kept.  Bit identity: row b, frames [0, T_b), equals what
+ * vp_melspec_cmn_f32 returns for that utterance alone (B = 1, L = n_b), in out and in out_bf16 -- the same frame kernel
+ * runs with a per-row length, and the mean is the same tile sums added in the same order. */
+int vp_melspec_cmn_ragged_f32(vp_ctx* ctx, const float* wav, const int32_t* n_samples, int B, int L, const vp_mel_opts* o,
+                              float* out, void* out_bf16, int32_t* n_frames, void* ws, size_t ws_bytes, vp_stream stream);
+
 /* ------------------------------------------------------------------------------------------------
  * conv1d as implicit GEMM with fused epilogue -- replaces, per launch, the reference chain
  *   Conv1d.forward (models/utils.py:65-93: reflect "same" pad + nn.Conv1D)  /  nn.Conv1D (tdnn.py:13-21)

@@ -10,6 +10,9 @@
 // (radix-4 stages, one radix-2 stage when n_fft/2 is not a power of 4), real-FFT unpack to the
 // n_fft/2+1 power bins, sparse mel bank (CSR), per-tile column sums for the CMN pass (shared with
 // the Fbank path).  The next frame's samples are fetched while the current one is transformed.
+// Ragged batches (vp_melspec_cmn_ragged_f32) run the SAME frame kernel with a per-row sample count: row b is then an
+// utterance of n_b samples (reflection folds at n_b, frames stop at T_b), so a frame's value and the order of every sum
+// are those of the utterance featurised alone -- the results agree bit for bit.
 #include "common.h"
 
 #include <math.h>
@@ -26,6 +29,7 @@ constexpr int MS_MAX_NNZ = 4096;
 
 struct MelArgs {
     const float* wav; float* out; float* psum;
+    const int* n_samples;     // ragged: [B] samples of each row's utterance (clamped to [0, L]); NULL: every row holds L
     const float* window;      // [n_fft], zero outside the centred win_length
     const float2* tw;         // [n_fft] e^{-2 pi i k / n_fft}
     const int* mel_start; const int* mel_bin0; const float* mel_w;
@@ -58,6 +62,12 @@ __global__ __launch_bounds__(WAVES * 64) void melspec_frames_kernel(MelArgs a) {
 
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int tile = blockIdx.x, b = blockIdx.y;
+    int Lb = a.L, Tb = a.T;                      // this row's samples and frames
+    if (a.n_samples) {
+        Lb = min(max(a.n_samples[b], 0), a.L);
+        Tb = Lb > NC ? 1 + Lb / a.hop : 0;       // n_b <= n_fft/2 cannot be reflect-padded: no frames
+        if (tile * MS_FRAMES_PER_WG >= Tb) return;    // workgroup-uniform: a tile past the utterance's end costs a branch
+    }
     for (int i = tid; i < NFFT; i += WAVES * 64) { s_tw[i] = a.tw[i]; s_win[i] = a.window[i]; }
     for (int i = tid; i < a.nnz; i += WAVES * 64) s_melw[i] = a.mel_w[i];
     for (int i = tid; i <= a.n_mels; i += WAVES * 64) s_mstart[i] = a.mel_start[i];
@@ -72,19 +82,19 @@ __global__ __launch_bounds__(WAVES * 64) void melspec_frames_kernel(MelArgs a) {
 
     float2 nxt[PPL];
     auto fetch = [&](int t) {                     // z[n] = x[2n] + i x[2n+1] of the centred, reflect-padded frame
-        const int base = min(t, a.T - 1) * a.hop - NC;
+        const int base = min(t, Tb - 1) * a.hop - NC;
 #pragma unroll
         for (int u = 0; u < PPL; ++u) {
             const int n = lane + 64 * u;
-            nxt[u].x = wav[reflect_idx(base + 2 * n, a.L)];
-            nxt[u].y = wav[reflect_idx(base + 2 * n + 1, a.L)];
+            nxt[u].x = wav[reflect_idx(base + 2 * n, Lb)];
+            nxt[u].y = wav[reflect_idx(base + 2 * n + 1, Lb)];
         }
     };
     fetch(tile * MS_FRAMES_PER_WG + wv);
 
     for (int fi = wv; fi < MS_FRAMES_PER_WG; fi += WAVES) {
         const int t = tile * MS_FRAMES_PER_WG + fi;
-        if (t >= a.T) break;                      // wave-uniform
+        if (t >= Tb) break;                       // wave-uniform
 #pragma unroll
         for (int u = 0; u < PPL; ++u) {
             const int n = lane + 64 * u;
@@ -179,6 +189,38 @@ __global__ __launch_bounds__(WAVES * 64) void melspec_frames_kernel(MelArgs a) {
 #pragma unroll
         for (int w = 0; w < WAVES; ++w) s += s_red[w * MS_MAX_MEL + tid];
         a.psum[((size_t)b * a.tiles + tile) * a.n_mels + tid] = s;
+    }
+}
+
+// CMN pass of a ragged batch.  The mean is formed exactly as fbank_cmn_kernel forms it for the utterance alone -- the
+// column sums of tiles 0 .. ceil(T_b / 16) - 1 added in ascending order, divided by (float)T_b -- so the result equals
+// the dense entry point's bit for bit; tiles past T_b were never written and are not read.  Rows t >= T_b are written
+// as zeros without being read.  Block (0, b) also publishes T_b.
+struct MelCmnRaggedArgs { float* out; bf16_t* out_bf16; const float* psum; const int* n_samples; int* n_frames; int L, T, tiles, hop, nc, n_mels; };
+
+__global__ __launch_bounds__(256) void melspec_cmn_ragged_kernel(MelCmnRaggedArgs a) {
+    __shared__ float s_mean[MS_MAX_MEL];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int Lb = min(max(a.n_samples[b], 0), a.L);
+    const int Tb = Lb > a.nc ? 1 + Lb / a.hop : 0;
+    if (blockIdx.x == 0 && tid == 0) a.n_frames[b] = Tb;
+    if (tid < a.n_mels) {
+        const int tiles_b = (Tb + MS_FRAMES_PER_WG - 1) / MS_FRAMES_PER_WG;
+        float s = 0.f;
+        for (int i = 0; i < tiles_b; ++i) s += a.psum[((size_t)b * a.tiles + i) * a.n_mels + tid];
+        s_mean[tid] = Tb > 0 ? s / (float)Tb : 0.f;
+    }
+    __syncthreads();
+    const int n = a.T * a.n_mels;
+    const int per_blk = (n + gridDim.x - 1) / gridDim.x;
+    const int e0 = blockIdx.x * per_blk, e1 = min(e0 + per_blk, n);
+    float* o = a.out + (size_t)b * n;
+    bf16_t* ob = a.out_bf16 ? a.out_bf16 + (size_t)b * n : nullptr;
+    for (int e = e0 + tid; e < e1; e += 256) {
+        const int t = e / a.n_mels;
+        const float v = t < Tb ? o[e] - s_mean[e - t * a.n_mels] : 0.f;
+        o[e] = v;
+        if (ob) ob[e] = (bf16_t)v;
     }
 }
 
@@ -297,9 +339,10 @@ size_t vp_mel_workspace_bytes(const vp_mel_opts* o, int B, int L) {
     return vp_align_up((size_t)B * (tiles > 0 ? tiles : 1) * o->n_mels * sizeof(float), 256);
 }
 
-int vp_melspec_cmn_f32(vp_ctx* ctx, const float* wav, const float* lens_ratio, int B, int L, const vp_mel_opts* o,
-                       float* out, void* out_bf16, void* ws, size_t ws_bytes, vp_stream stream) {
-    if (!ctx || !wav || !o || !out || B <= 0) VP_FAIL(ctx, VP_EINVAL, "melspec: bad arguments");
+// Dense (n_samples NULL: lens_ratio mask, n_frames unused) and ragged (n_samples, n_frames) entry points: the same checks and
+// the same frame kernel launch.
+static int melspec_cmn(vp_ctx* ctx, const float* wav, const float* lens_ratio, const int32_t* n_samples, int B, int L, const vp_mel_opts* o,
+                       float* out, void* out_bf16, int32_t* n_frames, void* ws, size_t ws_bytes, vp_stream stream) {
     if (L <= o->n_fft / 2) VP_FAIL(ctx, VP_EINVAL, "melspec: %d samples are too few for reflect padding of %d", L, o->n_fft / 2);
     if (B > 65535) VP_FAIL(ctx, VP_EINVAL, "melspec: batch %d > 65535", B);
     int rc = build_mel_tables(ctx, o);
@@ -309,7 +352,7 @@ int vp_melspec_cmn_f32(vp_ctx* ctx, const float* wav, const float* lens_ratio, i
     const int tiles = (T + MS_FRAMES_PER_WG - 1) / MS_FRAMES_PER_WG;
     hipStream_t st = (hipStream_t)stream;
     MelArgs a;
-    a.wav = wav; a.out = out; a.psum = (float*)ws; a.window = ctx->ms_window; a.tw = ctx->ms_twiddle;
+    a.wav = wav; a.out = out; a.psum = (float*)ws; a.n_samples = n_samples; a.window = ctx->ms_window; a.tw = ctx->ms_twiddle;
     a.mel_start = ctx->ms_mel_start; a.mel_bin0 = ctx->ms_mel_bin0; a.mel_w = ctx->ms_mel_w;
     a.B = B; a.L = L; a.T = T; a.tiles = tiles; a.hop = o->hop_length; a.n_mels = o->n_mels; a.nnz = ctx->ms_nnz;
     a.power = o->power;
@@ -318,7 +361,25 @@ int vp_melspec_cmn_f32(vp_ctx* ctx, const float* wav, const float* lens_ratio, i
     else if (o->n_fft == 1024) rc = launch_mel<512, 4>(ctx, a, st);
     else rc = launch_mel<1024, 2>(ctx, a, st);
     if (rc) return rc;
-    return vp_feat_cmn(ctx, out, out_bf16, (const float*)ws, lens_ratio, B, T, tiles, o->n_mels, st);
+    if (!n_samples) return vp_feat_cmn(ctx, out, out_bf16, (const float*)ws, lens_ratio, B, T, tiles, o->n_mels, st);
+    MelCmnRaggedArgs c{out, (bf16_t*)out_bf16, (const float*)ws, n_samples, n_frames, L, T, tiles, o->hop_length, o->n_fft / 2, o->n_mels};
+    int gx = (T * o->n_mels + 4095) / 4096;
+    if (gx < 1) gx = 1;
+    hipLaunchKernelGGL(melspec_cmn_ragged_kernel, dim3(gx, B), dim3(256), 0, st, c);
+    VP_LAUNCH_CHECK(ctx, "melspec_cmn_ragged");
+    return VP_OK;
+}
+
+int vp_melspec_cmn_f32(vp_ctx* ctx, const float* wav, const float* lens_ratio, int B, int L, const vp_mel_opts* o,
+                       float* out, void* out_bf16, void* ws, size_t ws_bytes, vp_stream stream) {
+    if (!ctx || !wav || !o || !out || B <= 0) VP_FAIL(ctx, VP_EINVAL, "melspec: bad arguments");
+    return melspec_cmn(ctx, wav, lens_ratio, nullptr, B, L, o, out, out_bf16, nullptr, ws, ws_bytes, stream);
+}
+
+int vp_melspec_cmn_ragged_f32(vp_ctx* ctx, const float* wav, const int32_t* n_samples, int B, int L, const vp_mel_opts* o, float* out,
+                              void* out_bf16, int32_t* n_frames, void* ws, size_t ws_bytes, vp_stream stream) {
+    if (!ctx || !wav || !n_samples || !n_frames || !o || !out || B <= 0) VP_FAIL(ctx, VP_EINVAL, "melspec_ragged: bad arguments");
+    return melspec_cmn(ctx, wav, nullptr, n_samples, B, L, o, out, out_bf16, n_frames, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

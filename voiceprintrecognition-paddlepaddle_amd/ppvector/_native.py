@@ -233,6 +233,8 @@ _PROTOS = {
     'vp_mel_workspace_bytes': (c_size_t, [C.POINTER(MelOpts), c_int, c_int]),
     'vp_melspec_cmn_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, C.POINTER(MelOpts), c_void_p,
                                    c_void_p, c_void_p, c_size_t, c_void_p]),
+    'vp_melspec_cmn_ragged_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, C.POINTER(MelOpts), c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_size_t, c_void_p]),
     'vp_conv1d_tiles_m': (c_int, [c_int, c_int]),
     'vp_conv1d_nseg': (c_int, [c_int]),
     'vp_conv1d_fwd': (c_int, [c_void_p, C.POINTER(Conv1dDesc), c_void_p]),

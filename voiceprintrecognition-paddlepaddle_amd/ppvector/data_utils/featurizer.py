@@ -146,50 +146,69 @@ class AudioFeaturizer(nn.Module):
             N.check(fn(ctx, N.ptr(wav), N.ptr(ratio), B, L, C.byref(self._opts), N.ptr(out), N.ptr(out16), N.ptr(ws),
                        ws.numel(), N.stream_ptr()), ctx)
         if self._feature_method == 'MFCC':
-            # paddle.audio.features.MFCC (featurizer.py:26-27): log-mel @ create_dct(n_mfcc, n_mels, norm='ortho').  The DCT is
-            # linear, so it commutes with the mean subtraction and the zeroed rows already applied to the log-mel features.
-            if self._dct is None or self._dct.device != wav.device:
-                n = torch.arange(F, dtype=torch.float64)
-                k = torch.arange(self._n_mfcc, dtype=torch.float64).unsqueeze(1)
-                dct = torch.cos(math.pi / F * (n + 0.5) * k)
-                dct[0] *= 1.0 / math.sqrt(2.0)
-                self._dct = (dct * math.sqrt(2.0 / F)).t().contiguous().float().to(wav.device)        # (n_mels, n_mfcc)
-            mf = torch.empty((B, T, self._n_mfcc), dtype=torch.float32, device=wav.device)
-            N.check(lib.vp_dense_f32(ctx, N.ptr(out), F, N.ptr(self._dct), 1, None, B * T, self._n_mfcc, F, N.VP_ACT_NONE, N.ptr(mf),
-                                     self._n_mfcc, N.stream_ptr()), ctx)
-            out, out16 = mf, (torch.empty_like(mf, dtype=torch.bfloat16) if want_bf16 else None)
-            if out16 is not None:
-                N.check(lib.vp_cast_f32_bf16(ctx, N.ptr(out), N.ptr(out16), out.numel(), N.stream_ptr()), ctx)
+            out, out16 = self._mfcc(out, want_bf16)
         if out16 is not None:
             out._vp_bf16 = out16
         return out
+
+    def _mfcc(self, logmel, want_bf16):
+        """paddle.audio.features.MFCC (featurizer.py:26-27): log-mel @ create_dct(n_mfcc, n_mels, norm='ortho').  The DCT is
+        linear, so it commutes with the mean subtraction and the zeroed rows already applied to the log-mel features (B, T, n_mels).
+        Returns (mfcc (B, T, n_mfcc) f32, its bf16 cast or None)."""
+        B, T, F = logmel.shape
+        lib, ctx = N.lib(), N.ctx(logmel.device)
+        if self._dct is None or self._dct.device != logmel.device:
+            n = torch.arange(F, dtype=torch.float64)
+            k = torch.arange(self._n_mfcc, dtype=torch.float64).unsqueeze(1)
+            dct = torch.cos(math.pi / F * (n + 0.5) * k)
+            dct[0] *= 1.0 / math.sqrt(2.0)
+            self._dct = (dct * math.sqrt(2.0 / F)).t().contiguous().float().to(logmel.device)        # (n_mels, n_mfcc)
+        mf = torch.empty((B, T, self._n_mfcc), dtype=torch.float32, device=logmel.device)
+        N.check(lib.vp_dense_f32(ctx, N.ptr(logmel), F, N.ptr(self._dct), 1, None, B * T, self._n_mfcc, F, N.VP_ACT_NONE, N.ptr(mf),
+                                 self._n_mfcc, N.stream_ptr()), ctx)
+        mf16 = torch.empty_like(mf, dtype=torch.bfloat16) if want_bf16 else None
+        if mf16 is not None:
+            N.check(lib.vp_cast_f32_bf16(ctx, N.ptr(mf), N.ptr(mf16), mf.numel(), N.stream_ptr()), ctx)
+        return mf, mf16
 
     def forward_ragged(self, waveforms, n_samples, want_bf16=False):
         """The training loader's semantics for a ragged batch: utterance b occupies the first n_samples[b] samples of row b;
         it is featurised as if alone (time mean over ITS frames -- the reference's per-utterance call, reader.py:102-103) and
         the rows past its last frame are zero (collate_fn.py:5-23).  Returns (features (B, T, F), input_lens (B,) int64).
-        One batched launch for 'Fbank'; other methods run utterance by utterance and are packed by vp_pad_batch."""
+        One batched launch for every built method: 'Fbank', and the mel family ('MelSpectrogram', 'LogMelSpectrogram', 'MFCC'
+        with its DCT over the whole batch), whose rows equal the utterance's own forward() bit for bit.  With want_bf16 the
+        bf16 copy is attached as ``._vp_bf16``.  A mel-family utterance of n_fft/2 samples or fewer cannot be reflect-padded and
+        raises, as its own forward() does; lengths that arrive as a GPU tensor cost one readback of their minimum for that."""
+        if self._opts is None:
+            raise NotImplementedError(f'feature_method {self._feature_method} is not built on the HIP engine yet '
+                                      '(Fbank is); there is no CPU fallback')
         if not waveforms.is_cuda:
             raise N.VpmiError('AudioFeaturizer needs GPU tensors: the engine has no CPU fallback')
         wav = waveforms.contiguous().float()
         B, L = wav.shape
+        mel = self._feature_method != 'Fbank'
+        if mel:
+            shortest = min(int(torch.as_tensor(n_samples).min()), L)
+            if shortest <= self._opts.n_fft // 2:
+                raise N.VpmiError(f'libvpmi error {N.VP_EINVAL}: melspec: {shortest} samples are too few for reflect padding of '
+                                  f'{self._opts.n_fft // 2}')
         ns = torch.as_tensor(n_samples).to(device=wav.device, dtype=torch.int32).contiguous()
-        if self._feature_method != 'Fbank':
-            from ppvector.data_utils.collate_fn import collate_fn
-            feats = [self.forward(wav[b, :int(n)])[0] for b, n in enumerate(ns.tolist())]
-            out, _, lens = collate_fn([(f, 0) for f in feats])
-            return out, lens
         lib, ctx = N.lib(), N.ctx(wav.device)
-        T = lib.vp_fbank_num_frames(C.byref(self._opts), L)
+        T = (lib.vp_mel_num_frames if mel else lib.vp_fbank_num_frames)(C.byref(self._opts), L)
         if T <= 0:
             raise ValueError(f'{L} samples are shorter than one analysis window')
         F = self._opts.n_mels
+        mfcc = self._feature_method == 'MFCC'
         out = torch.empty((B, T, F), dtype=torch.float32, device=wav.device)
-        out16 = torch.empty((B, T, F), dtype=torch.bfloat16, device=wav.device) if want_bf16 else None
+        out16 = torch.empty((B, T, F), dtype=torch.bfloat16, device=wav.device) if want_bf16 and not mfcc else None
         nf = torch.empty((B,), dtype=torch.int32, device=wav.device)
-        ws = self._ws.get(lib.vp_fbank_workspace_bytes(C.byref(self._opts), B, L), wav.device)
-        N.check(lib.vp_fbank_cmn_ragged_f32(ctx, N.ptr(wav), N.ptr(ns), B, L, C.byref(self._opts), N.ptr(out), N.ptr(out16), N.ptr(nf),
-                                            N.ptr(ws), ws.numel(), N.stream_ptr()), ctx)
+        nws = (lib.vp_mel_workspace_bytes if mel else lib.vp_fbank_workspace_bytes)(C.byref(self._opts), B, L)
+        ws = self._ws.get(nws, wav.device)
+        fn = lib.vp_melspec_cmn_ragged_f32 if mel else lib.vp_fbank_cmn_ragged_f32
+        N.check(fn(ctx, N.ptr(wav), N.ptr(ns), B, L, C.byref(self._opts), N.ptr(out), N.ptr(out16), N.ptr(nf), N.ptr(ws), ws.numel(),
+                   N.stream_ptr()), ctx)
+        if mfcc:
+            out, out16 = self._mfcc(out, want_bf16)             # zero rows stay zero: the DCT has no bias
         if out16 is not None:
             out._vp_bf16 = out16
         return out, nf.to(torch.int64)

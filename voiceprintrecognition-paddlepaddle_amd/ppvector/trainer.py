@@ -192,8 +192,10 @@ class PPVectorTrainer(object):
         torch.cuda.current_stream().synchronize()                 # the pinned buffer is reused by the next batch
         return [dev[o:o + n] for o, n in zip(offs[:-1].tolist(), lens)]
 
-    def extract_features(self, save_dir='dataset/features', max_duration=100):
-        """trainer.py:134-160: dump every list's features to .npy and write '<list>_features.txt'."""
+    def extract_features(self, save_dir='dataset/features', max_duration=100, batch_size=1):
+        """trainer.py:134-160: dump every list's features to .npy and write '<list>_features.txt'.  batch_size (an extension; 1 = the
+        reference's one utterance at a time) featurises that many consecutive items in one ragged batch and writes each
+        utterance's own frames: the same files and list lines."""
         self.audio_featurizer = AudioFeaturizer(feature_method=self.configs.preprocess_conf.feature_method,
                                                 method_args=self.configs.preprocess_conf.get('method_args', {}))
         conf = self.configs.dataset_conf
@@ -203,14 +205,21 @@ class PPVectorTrainer(object):
             ds = PPVectorDataset(data_list_path=data_list, audio_featurizer=self.audio_featurizer, mode='extract_feature', **dataset_args)
             save_data_list = data_list.replace('.txt', '_features.txt')
             with open(save_data_list, 'w', encoding='utf-8') as f:
-                for i in range(len(ds)):
-                    item = ds[i]
-                    feats, _ = self._features([item], ds)
-                    label = int(item['label'])
-                    save_path = os.path.join(save_dir, str(label), f'{int(time.time() * 1000)}_{i}.npy').replace('\\', '/')
-                    os.makedirs(os.path.dirname(save_path), exist_ok=True)
-                    np.save(save_path, feats[0].cpu().numpy())
-                    f.write(f'{save_path}\t{label}\n')
+                for i0 in range(0, len(ds), max(int(batch_size), 1)):
+                    items = [ds[i] for i in range(i0, min(i0 + max(int(batch_size), 1), len(ds)))]
+                    feats, _ = self._features(items, ds)
+                    feats = feats.cpu().numpy()
+                    frames = self._last_frames or [feats.shape[1]] * len(items)     # None: equal lengths, every row is whole
+                    for j, item in enumerate(items):
+                        label = int(item['label'])
+                        stamp = int(time.time() * 1000)
+                        save_path = os.path.join(save_dir, str(label), f'{stamp}_{i0 + j}.npy').replace('\\', '/')
+                        while os.path.exists(save_path):        # the three lists share save_dir and restart the index: a batch is
+                            stamp += 1                          # quick enough for two of them to meet in one millisecond
+                            save_path = os.path.join(save_dir, str(label), f'{stamp}_{i0 + j}.npy').replace('\\', '/')
+                        os.makedirs(os.path.dirname(save_path), exist_ok=True)
+                        np.save(save_path, feats[j, :frames[j]])
+                        f.write(f'{save_path}\t{label}\n')
             _LOG.info('%s列表中的数据已提取特征完成，新列表为：%s', data_list, save_data_list)
 
     # ------------------------------------------------------------------------------------------------ model
