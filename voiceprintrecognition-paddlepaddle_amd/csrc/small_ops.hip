@@ -314,8 +314,9 @@ __global__ __launch_bounds__(256) void im2col_hl_kernel(Im2colArgs a) {
 // ---------------------------------------------------------------- ASP softmax over time + weighted stats
 // pooling.py:114-123: attn = softmax_t(logits); mean = sum attn x; std = sqrt(clip(sum attn (x-mean)^2, eps)).
 // One workgroup = 64 channels of one utterance; the 4 waves split the frames, online softmax per
-// lane, merged through LDS.  x is centred on `center` (the plain time mean) to keep the variance
-// well conditioned in f32.
+// lane, merged through LDS.  x is centred on `center` (the plain time mean; the inference engines) or, with none given, on the
+// utterance's first frame of the channel, to keep the sums well conditioned in f32: raw E[x^2] - E[x]^2 loses (mean / std)^2 of
+// the std's relative precision.  With no centre given the variance comes from a second pass about the mean (docs/pooling_stats.md).
 template <typename T>
 struct AspArgs {
     const float* logits; const T* x; const float* center; float* pooled;
@@ -330,9 +331,10 @@ __global__ __launch_bounds__(256) void asp_softmax_stats_kernel(AspArgs<T> a) {
     const int c = blockIdx.x * 64 + lane;
     const bool ok = c < a.C;
     const int cc = ok ? c : 0;
-    const float mu0 = a.center ? a.center[(size_t)b * a.ldc + cc] : 0.f;
-    float mx = -INFINITY, s0 = 0.f, s1 = 0.f, s2 = 0.f;
     const size_t row0 = (size_t)b * a.T_;
+    // no centre given (the training entry points): the utterance's own first frame of the channel, as time_moments4_kernel does
+    const float mu0 = a.center ? a.center[(size_t)b * a.ldc + cc] : vp_to_f32(a.x[row0 * a.ldx + a.xoff + cc]);
+    float mx = -INFINITY, s0 = 0.f, s1 = 0.f, s2 = 0.f;
     for (int t = wv; t < a.T_; t += 4) {
         const float e = a.logits[(row0 + t) * a.C + cc];
         const float xv = vp_to_f32(a.x[(row0 + t) * a.ldx + a.xoff + cc]) - mu0;
@@ -346,6 +348,33 @@ __global__ __launch_bounds__(256) void asp_softmax_stats_kernel(AspArgs<T> a) {
     }
     sm[wv][0][lane] = mx; sm[wv][1][lane] = s0; sm[wv][2][lane] = s1; sm[wv][3][lane] = s2;
     __syncthreads();
+    if (!a.center) {
+        // second pass about the mean just found: sum p (x - mu)^2 has no cancellation left, whatever the softmax weighs (a peaked
+        // one puts mu far from any fixed centre: var << (mu - centre)^2, and s2 / s0 - md^2 loses var's leading digits)
+        const float M = fmaxf(fmaxf(sm[0][0][lane], sm[1][0][lane]), fmaxf(sm[2][0][lane], sm[3][0][lane]));
+        float t0 = 0.f, t1 = 0.f;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const float mw = sm[w][0][lane];
+            const float f = (mw == -INFINITY) ? 0.f : expf(mw - M);
+            t0 += sm[w][1][lane] * f; t1 += sm[w][2][lane] * f;
+        }
+        const float md = t1 / t0;
+        float v = 0.f;
+        for (int t = wv; t < a.T_; t += 4) {
+            const float p = expf(a.logits[(row0 + t) * a.C + cc] - M);
+            const float d = vp_to_f32(a.x[(row0 + t) * a.ldx + a.xoff + cc]) - mu0 - md;
+            v += p * d * d;
+        }
+        sm[wv][3][lane] = v;                    // (the first pass's s2: not read on this path)
+        __syncthreads();
+        if (wv == 0 && ok) {
+            const float var = (sm[0][3][lane] + sm[1][3][lane] + sm[2][3][lane] + sm[3][3][lane]) / t0;
+            a.pooled[(size_t)b * 2 * a.C + c] = mu0 + md;
+            a.pooled[(size_t)b * 2 * a.C + a.C + c] = sqrtf(fmaxf(var, a.eps));
+        }
+        return;
+    }
     if (wv == 0 && ok) {
         float M = fmaxf(fmaxf(sm[0][0][lane], sm[1][0][lane]), fmaxf(sm[2][0][lane], sm[3][0][lane]));
         float t0 = 0.f, t1 = 0.f, t2 = 0.f;
@@ -906,8 +935,8 @@ __global__ __launch_bounds__(512) void asp_softmax_stats_reg_kernel(AspArgs<floa
     const int c = blockIdx.x * 64 + lane;
     const bool ok = c < a.C;
     const int cc = ok ? c : 0;
-    const float mu0 = a.center ? a.center[(size_t)b * a.ldc + cc] : 0.f;
     const size_t row0 = (size_t)b * a.T_;
+    const float mu0 = a.center ? a.center[(size_t)b * a.ldc + cc] : vp_to_f32(xg[row0 * a.ldx + a.xoff + cc]);    // (as in the streaming kernel)
     float ev[NT], xv[NT];
 #pragma unroll
     for (int i = 0; i < NT; ++i) {
@@ -932,6 +961,31 @@ __global__ __launch_bounds__(512) void asp_softmax_stats_reg_kernel(AspArgs<floa
     }
     sm[1][rg][lane] = s0; sm[2][rg][lane] = s1; sm[3][rg][lane] = s2;
     __syncthreads();
+    if (!a.center) {
+        // the variance from a second pass over the registers, about the mean just found (see asp_softmax_stats_kernel)
+        float t0 = 0.f, t1 = 0.f;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) { t0 += sm[1][q][lane]; t1 += sm[2][q][lane]; }
+        const float md = t1 / t0;
+        float v = 0.f;
+#pragma unroll
+        for (int i = 0; i < NT; ++i) {
+            if (rg + 8 * i < a.T_) {
+                const float p = expf(ev[i] - mx), d = xv[i] - mu0 - md;
+                v += p * d * d;
+            }
+        }
+        sm[0][rg][lane] = v;                    // (the maxima were last read before the barrier above)
+        __syncthreads();
+        if (rg == 0 && ok) {
+            float t2 = 0.f;
+#pragma unroll
+            for (int q = 0; q < 8; ++q) t2 += sm[0][q][lane];
+            a.pooled[(size_t)b * 2 * a.C + c] = mu0 + md;
+            a.pooled[(size_t)b * 2 * a.C + a.C + c] = sqrtf(fmaxf(t2 / t0, a.eps));
+        }
+        return;
+    }
     if (rg == 0 && ok) {
         float t0 = 0.f, t1 = 0.f, t2 = 0.f;
 #pragma unroll
