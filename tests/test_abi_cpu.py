@@ -1,6 +1,7 @@
 """CPU tests of the drop-in boundary: the C-ABI library loads and exports every symbol that
 include/vpmi.h declares (no compute calls: there is no GPU here), host-side logic of the Python
 mirror (registries, config loading, schedules, metrics, parameter naming)."""
+import ctypes as C
 import os
 import re
 
@@ -38,6 +39,102 @@ def test_struct_sizes_match_header_layout():
     assert C.sizeof(N.FbankOpts) == 9 * 4
     assert C.sizeof(N.SeRes2Block) == 17 * C.sizeof(N.TdnnLayer) + 4 * 8
     assert C.sizeof(N.AspWeights) == C.sizeof(N.TdnnLayer) + 3 * 8 + 8
+
+
+def _binding():
+    from ppvector import _native as N
+    return {c: getattr(N, py) for c, py in N.STRUCT_CLASSES.items()}, N._PROTOS
+
+
+def test_binding_matches_what_the_compiler_sees(tmp_path):
+    """The binding is parsed from include/vpmi.h, so the independent witness is the C++ compiler (tests/abi_compiler.py): sizeof of
+    every struct, offset and size of every field, and the return / parameter classes of every function, all of them."""
+    from tests import abi_compiler as ac
+    structs, protos = _binding()
+    sizes, members, sigs = ac.compiler_view({c: [f for f, _ in cls._fields_] for c, cls in structs.items()}, list(protos), tmp_path)
+    want_sizes, want_members, want_sigs = ac.ctypes_view(structs, protos)
+    assert len(sizes) == len(structs) == 20
+    assert len(members) == sum(len(cls._fields_) for cls in structs.values()) >= 248
+    assert len(sigs) == len(protos) >= 166
+    assert sizes == want_sizes, {k: (sizes[k], want_sizes[k]) for k in sizes if sizes[k] != want_sizes[k]}
+    assert members == want_members, {k: (members[k], want_members[k]) for k in members if members[k] != want_members[k]}
+    assert sigs == want_sigs, {k: (sigs[k], want_sigs[k]) for k in sigs if sigs[k] != want_sigs[k]}
+
+
+def test_constants_come_from_the_header():
+    from ppvector import _native as N
+    assert (N.VPMI_VERSION, N.VP_OK, N.VP_EWORKSPACE, N.VP_HL32, N.VP_ACT_SILU, N.VP_LOSS_SUBCENTER) == (100, 0, -5, 3, 5, 4)
+    assert (N.VP_MAX_RES2, N.VP_MAX_CAM_LAYERS, N.VP_MAX_R2N_SCALE, N.VP_CONV_K128X256_RING) == (15, 64, 8, 3)
+    assert (N.c_void_p, N.c_int, N.c_float, N.c_size_t) == (C.c_void_p, C.c_int, C.c_float, C.c_size_t)
+    assert N.lib is N.load_library
+
+
+SMALL = {'vp_a': 'A', 'vp_b': 'B'}
+
+
+@pytest.mark.parametrize('text,complaint', [
+    ('typedef struct { double x; } vp_a;', 'double'),                                    # a scalar outside the type table
+    ('int vp_f(double x);', 'double'),
+    ('int vp_f(int (*cb)(int), int n);', 'vp_f'),                                        # a declaration it cannot consume
+    ('typedef struct { int (*cb)(int); } vp_a;', 'cb'),
+    ('typedef struct { int x[VP_MAX_NOPE]; } vp_a;', 'VP_MAX_NOPE'),                     # an array bound that is no known constant
+    ('typedef struct { int x; } vp_c;', 'vp_c'),                                         # a struct without a class name
+    ('typedef struct { vp_b b; int n; } vp_a;\ntypedef struct { int x; } vp_b;', 'vp_b'),  # nested before it is declared
+    ('int vp_f(const vp_b* b);\ntypedef struct { int x; } vp_b;', 'vp_b'),
+    ('typedef struct { int x[VP_MAX_N]; } vp_a;\n#define VP_MAX_N 4', 'VP_MAX_N'),        # a constant defined after its use
+    ('int vp_f(unsigned n);', 'unsigned'),
+    ('int vp_f(int);', 'vp_f'),                                                          # unnamed parameter: not this header's dialect
+    ('#define VP_MAX_X 1.5', 'VP_MAX_X'),
+    ('enum { VP_X = 1 << 3 };', 'VP_X'),
+    ('int vp_f(int n);\nstatic inline int vp_g(int n) { return n; }', 'vp_g'),
+])
+def test_parser_refuses_what_it_does_not_know(text, complaint):
+    from ppvector._abi import AbiError, parse
+    with pytest.raises(AbiError, match=complaint):
+        parse(text, SMALL)
+
+
+def test_parser_reads_the_dialect_of_the_header():
+    from ppvector._abi import parse
+    a = parse("""/* a comment with ; and ( in it */
+#ifndef X_H
+#define X_H
+#include <stddef.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define VP_MAX_N 3
+typedef struct vp_ctx vp_ctx;
+typedef void* vp_stream;
+enum { VP_P = 0, VP_Q = -2 };
+typedef struct { int a, b; const float* w[2]; long long n; } vp_b;
+typedef struct { vp_b one, two; vp_b many[VP_MAX_N - 1]; int tail[VP_MAX_N]; } vp_a;
+const char* vp_text(vp_ctx* ctx);
+void vp_fill(vp_a* a, const vp_b* b,
+             const void* const* srcs, int16_t* pcm, size_t n /* bytes */, float x, long long m, vp_stream stream);
+vp_ctx* vp_make(void);
+#ifdef __cplusplus
+}
+#endif
+#endif
+""", SMALL)
+    A, B = a.structs['vp_a'], a.structs['vp_b']
+    assert (A.__name__, B.__name__) == ('A', 'B') and a.consts == {'VP_MAX_N': 3, 'VP_P': 0, 'VP_Q': -2}
+    assert [f for f, _ in B._fields_] == ['a', 'b', 'w', 'n'] and C.sizeof(B) == 8 + 16 + 8
+    assert [f for f, _ in A._fields_] == ['one', 'two', 'many', 'tail'] and C.sizeof(A) == 4 * 32 + 3 * 4 + 4
+    assert a.protos == {'vp_text': (C.c_char_p, [C.c_void_p]),
+                        'vp_fill': (None, [C.POINTER(A), C.POINTER(B), C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_longlong, C.c_void_p]),
+                        'vp_make': (C.c_void_p, [])}
+
+
+def test_stale_library_is_refused(monkeypatch):
+    """A lib/libvpmi.so older than the header it is loaded against: vp_version() != VPMI_VERSION raises, the library is not kept."""
+    from ppvector import _native as N
+    monkeypatch.setattr(N, '_lib', None)
+    monkeypatch.setattr(N, 'VPMI_VERSION', 101)
+    with pytest.raises(N.VpmiError, match='version 100'):
+        N.load_library()
+    assert N._lib is None
 
 
 def test_hl32_packing_matches_the_header_definition():

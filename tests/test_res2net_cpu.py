@@ -3,7 +3,6 @@ model's construction from the res2net.yml sections, its state-dict names, its re
 import ctypes as C
 import json
 import os
-import re
 
 import numpy as np
 import pytest
@@ -113,42 +112,21 @@ def test_feature_bins_follow_the_reference_shapes():
         assert feature_bins(F) == x.shape[2], F
 
 
-def _header_struct_size(name):
-    """sizeof(name) from include/vpmi.h, computed with ctypes from the header's own field list (pointers, ints, nested structs)."""
+def _header_struct_size(name, workdir):
+    """sizeof(name) and its field names in offset order as the C++ compiler lays include/vpmi.h out (tests/abi_compiler.py)."""
     from ppvector import _native as N
-    hdr = open(os.path.join(ROOT, 'include', 'vpmi.h')).read()
-    hdr = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
-    body = re.search(r'typedef struct \{([^}]*)\}\s*' + name + ';', hdr).group(1)
-    consts = {'VP_MAX_R2N_BLOCKS': N.VP_MAX_R2N_BLOCKS, 'VP_MAX_R2N_SCALE': N.VP_MAX_R2N_SCALE}
-    types = {'vp_tdnn_layer': N.TdnnLayer, 'vp_asp_weights': N.AspWeights, 'vp_r2n_block': N.R2nBlock}
-    fields = []
-    for decl in body.split(';'):
-        decl = decl.strip()
-        if not decl:
-            continue
-        typ, rest = decl.split(None, 1) if not decl.startswith('const ') else ('const float*', decl.split('*', 1)[1])
-        for v in rest.split(','):
-            v = v.strip()
-            if typ.endswith('*') or v.startswith('*'):
-                t = C.c_void_p
-            else:
-                t = types.get(typ, C.c_int)
-            m = re.match(r'\**(\w+)(?:\[(\w+)\])?', v)
-            if m.group(2):
-                t = t * consts.get(m.group(2), int(m.group(2)) if m.group(2).isdigit() else 0)
-            fields.append((m.group(1), t))
-
-    class S(C.Structure):
-        _fields_ = fields
-    return C.sizeof(S), [f[0] for f in fields]
+    from tests import abi_compiler as ac
+    fields = [f for f, _ in getattr(N, N.STRUCT_CLASSES[name])._fields_]
+    sizes, members, _ = ac.compiler_view({name: fields}, [], workdir)
+    return sizes[name], sorted(fields, key=lambda f: members[name, f][0])
 
 
-def test_struct_sizes_match_header():
+def test_struct_sizes_match_header(tmp_path):
     from ppvector import _native as N
-    size, names = _header_struct_size('vp_r2n_block')
+    size, names = _header_struct_size('vp_r2n_block', tmp_path)
     assert names == [f[0] for f in N.R2nBlock._fields_]
     assert C.sizeof(N.R2nBlock) == size == (3 + N.VP_MAX_R2N_SCALE) * C.sizeof(N.TdnnLayer) + 5 * 4 + 4
-    size, names = _header_struct_size('vp_res2net_weights')
+    size, names = _header_struct_size('vp_res2net_weights', tmp_path)
     assert names == [f[0] for f in N.Res2netWeights._fields_]
     assert C.sizeof(N.Res2netWeights) == size
 
