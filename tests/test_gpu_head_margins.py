@@ -1,9 +1,9 @@
 """GPU tests of the cosine head + margin losses at PLANTED target cosines and at the edges of the class / row tiling, against the float64
 reference of tests/head_oracle.py (pinned on the CPU by tests/test_head_oracle_cpu.py).  Run with -m gpu on an MI355X.
 
-The margin arithmetic exists five times (head_tile_fwd / head_tile_bwd in csrc/head_tiled.hip, aam_ce_rows / aam_ce_bwd_rows in
-csrc/head.hip, margin_out / sphere_term in csrc/losses.hip) and Python picks by shape.  Every test goes through the product's objects
-and asserts which path ran:
+The margin arithmetic is written once (vp_aam_margin, csrc/head_common.h) and has five users (head_tile_fwd / head_tile_bwd in
+csrc/head_tiled.hip, aam_ce_bwd_rows in csrc/head.hip, margin_out / sphere_term in csrc/losses.hip); Python picks by shape.  Every test
+goes through the product's objects and asserts which path ran:
   P1  evaluation, class-tiled   SpeakerIdentification.eval() -> AAMLoss           outputs.pred set, no 'logits' key
   P2  training, class-tiled     SpeakerIdentification.train() -> AAMLoss           outputs.pred set (HeadLoss.apply(..)[1].numel() == B)
   P3  training, logits tensor   the same with B > 128, D != 192 or VPMI_HEAD_UNTILED  outputs.pred None (.. numel() == 0), no 'logits' key

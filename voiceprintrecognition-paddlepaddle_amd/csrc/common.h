@@ -155,6 +155,8 @@ int vp_asp_fused_bf16(vp_ctx* ctx, const void* h, const void* w, const float* bi
                       const float* center, int ldc, int B, int T, int C, int att, float eps, float* pooled,
                       hipStream_t st);
 int vp_row_inv_norm(vp_ctx* ctx, const float* x, int rows, int D, int ld, float eps, float* inv, hipStream_t st);
+// out[0] = mean ? sum / n : sum of n row values (head.hip; the head and the loss family reduce their row losses with it)
+int vp_reduce_rows(vp_ctx* ctx, const float* v, int n, int mean, float* out, hipStream_t st);
 int vp_conv3x3_c32_bf16(vp_ctx* ctx, const void* x, void* y, const vp_tdnn_layer* conv, const void* res, int relu,
                         const vp_tdnn_layer* shortcut, void* y2, int B, int T, int F_in, int stride_f, const void* c1_feats,
                         const float* c1_w, const float* c1_b, const float* c1_scale, const float* c1_shift, hipStream_t st);

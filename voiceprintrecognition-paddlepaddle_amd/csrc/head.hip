@@ -8,7 +8,7 @@
 // CrossEntropyLoss(label_smoothing), mean), and the scoring loops trainer.py:416-423 / predict.py:282.
 // The (B, C) logits are produced in exact f32 on the f32 matrix cores and read once by the loss
 // kernel (online log-sum-exp per row, fixed-order reductions).
-#include "common.h"
+#include "head_common.h"
 
 #include <math.h>
 
@@ -43,128 +43,68 @@ __global__ __launch_bounds__(256) void col_inv_norm_kernel(const float* w, int D
     }
 }
 
-struct AamArgs {
-    const float* logits; const long long* labels; float* row_loss;
-    int B, C; float cos_m, sin_m, th, mmm, scale, ls; int easy;
-    const float* mt;                 // device margin table (vp_set_margin_table) or NULL: the launch scalars above
-};
-
-__global__ __launch_bounds__(256) void aam_ce_rows_kernel(AamArgs a) {
-    __shared__ float sm[3][4];
-    if (a.mt) { a.cos_m = a.mt[1]; a.sin_m = a.mt[2]; a.th = a.mt[3]; a.mmm = a.mt[4]; }
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const float* row = a.logits + (size_t)b * a.C;
-    const int y = (int)a.labels[b];
-    float mx = -INFINITY, se = 0.f, so = 0.f;       // running max, sum exp(out - mx), sum out
-    for (int c = tid; c < a.C; c += 256) {
-        const float cs = row[c];
-        float o = cs;
-        if (c == y) {
-            const float sine = sqrtf(fmaxf(1.f - cs * cs, 0.f));
-            const float phi = cs * a.cos_m - sine * a.sin_m;
-            o = a.easy ? (cs > 0.f ? phi : cs) : (cs > a.th ? phi : cs - a.mmm);
-        }
-        o *= a.scale;
-        so += o;
-        if (o > mx) { se = se * expf(mx - o) + 1.f; mx = o; }
-        else se += expf(o - mx);
-    }
-    // wave merge, then the 4 waves (fixed order)
-    const float wmx = vp_wave_max(mx);
-    se = vp_wave_sum(mx == -INFINITY ? 0.f : se * expf(mx - wmx));
-    so = vp_wave_sum(so);
-    if (lane == 0) { sm[0][wv] = wmx; sm[1][wv] = se; sm[2][wv] = so; }
-    __syncthreads();
-    if (tid == 0) {
-        float M = fmaxf(fmaxf(sm[0][0], sm[0][1]), fmaxf(sm[0][2], sm[0][3]));
-        float S = 0.f, O = 0.f;
-        for (int w = 0; w < 4; ++w) {
-            S += (sm[0][w] == -INFINITY) ? 0.f : sm[1][w] * expf(sm[0][w] - M);
-            O += sm[2][w];
-        }
-        const float lse = M + logf(S);
-        // target logit, recomputed by one thread (cheap, keeps the reduction single-pass)
-        const float cs = row[y];
-        const float sine = sqrtf(fmaxf(1.f - cs * cs, 0.f));
-        const float phi = cs * a.cos_m - sine * a.sin_m;
-        float oy = a.easy ? (cs > 0.f ? phi : cs) : (cs > a.th ? phi : cs - a.mmm);
-        oy *= a.scale;
-        // -sum_c q_c log p_c,  q = (1 - ls) onehot + ls / C
-        const float nll = lse - oy;
-        const float smooth = lse - O / (float)a.C;
-        a.row_loss[b] = (1.f - a.ls) * nll + a.ls * smooth;
-    }
-}
-
-__global__ __launch_bounds__(256) void mean_kernel(const float* v, int n, float* out) {
+// out[0] = mean ? sum / n : sum of n row values, fixed order: the one reduce of head.hip, head_tiled.hip and losses.hip
+// (vp_reduce_rows).  losses.hip multiplied by 1 / n before it shared this kernel: the loss scalar of vp_margin_ce_* and vp_sphereface2
+// moved by at most 1 ulp with it, and not at all where n is a power of two.
+__global__ __launch_bounds__(256) void reduce_rows_kernel(const float* v, int n, int mean, float* out) {
     __shared__ float sm[4];
     float s = 0.f;
     for (int i = threadIdx.x; i < n; i += 256) s += v[i];
     s = vp_wave_sum(s);
     if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = s;
     __syncthreads();
-    if (threadIdx.x == 0) out[0] = (sm[0] + sm[1] + sm[2] + sm[3]) / (float)n;
+    if (threadIdx.x == 0) {
+        const float t = sm[0] + sm[1] + sm[2] + sm[3];
+        out[0] = mean ? t / (float)n : t;
+    }
 }
 
-// ------------------------------------------------------------------------------------------------ backward
-// d loss / d cos for one row, pre-multiplied by the column inverse norms (what both backward GEMMs consume):
+// ------------------------------------------------------------------------------------------------ AAM rows: value and backward
+// One workgroup per row of the formed cosines.  Row loss (optional), and with G the gradient d loss / d cos, pre-multiplied by the
+// column inverse norms when cinv is given (what both backward GEMMs consume):
 //   out_c = scale * (c == y ? margin(cos_c) : cos_c);  p = softmax(out);  q = (1 - ls) onehot + ls / C
 //   G[b][c] = gscale / B * (p_c - q_c) * scale * d margin / d cos * cinv[c]
+// G == NULL: the forward value alone (vp_aam_ce_fwd).
+// Not merged with margin_ce_rows_kernel (losses.hip, kind AAM, K = 1): that one folds scale into dm, this one into k, and carries cinv
+// -- one kernel for both would move gradient bits.
 struct AamBwdArgs {
     const float* logits; const long long* labels; const float* cinv; float* G; float* row_loss;
-    int B, C; float cos_m, sin_m, th, mmm, scale, ls, gscale; int easy;
-    const float* mt;
+    int B, C; VpMargin mg; float scale, ls, gscale; int easy;
+    const float* mt;                 // device margin table (vp_set_margin_table) or NULL: the launch scalars above
 };
 
 __global__ __launch_bounds__(256) void aam_ce_bwd_rows_kernel(AamBwdArgs a) {
     __shared__ float sm[3][4];
     __shared__ float s_lse;
-    if (a.mt) { a.cos_m = a.mt[1]; a.sin_m = a.mt[2]; a.th = a.mt[3]; a.mmm = a.mt[4]; }
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    vp_margin_override(a.mg, a.mt, false);
+    const int b = blockIdx.x, tid = threadIdx.x;
     const float* row = a.logits + (size_t)b * a.C;
     const int y = (int)a.labels[b];
     auto out_of = [&](int c, float cs, float& dm) {
-        float o = cs;
         dm = 1.f;
-        if (c == y) {
-            const float sine = sqrtf(fmaxf(1.f - cs * cs, 0.f));
-            const float phi = cs * a.cos_m - sine * a.sin_m;
-            const bool use_phi = a.easy ? (cs > 0.f) : (cs > a.th);
-            o = use_phi ? phi : (a.easy ? cs : cs - a.mmm);
-            if (use_phi) dm = a.cos_m + cs * a.sin_m / sine;
-        }
-        return o * a.scale;
+        return (c == y ? vp_aam_margin(a.mg, a.easy, cs, dm) : cs) * a.scale;
     };
-    float mx = -INFINITY, se = 0.f, so = 0.f;
+    float mx = -INFINITY, se = 0.f, so = 0.f;       // running max, sum exp(out - mx), sum out
     for (int c = tid; c < a.C; c += 256) {
         float dm;
         const float o = out_of(c, row[c], dm);
         so += o;
-        if (o > mx) { se = se * expf(mx - o) + 1.f; mx = o; }
-        else se += expf(o - mx);
+        vp_lse_step(o, mx, se);
     }
-    const float wmx = vp_wave_max(mx);
-    se = vp_wave_sum(mx == -INFINITY ? 0.f : se * expf(mx - wmx));
-    so = vp_wave_sum(so);
-    if (lane == 0) { sm[0][wv] = wmx; sm[1][wv] = se; sm[2][wv] = so; }
-    __syncthreads();
+    float lse, O;
+    vp_lse_merge(mx, se, so, sm, lse, O);
     if (tid == 0) {
-        const float M = fmaxf(fmaxf(sm[0][0], sm[0][1]), fmaxf(sm[0][2], sm[0][3]));
-        float S = 0.f, O = 0.f;
-        for (int w = 0; w < 4; ++w) {
-            S += (sm[0][w] == -INFINITY) ? 0.f : sm[1][w] * expf(sm[0][w] - M);
-            O += sm[2][w];
-        }
-        const float lse = M + logf(S);
         s_lse = lse;
         if (a.row_loss) {
+            // -sum_c q_c log p_c; the target logit is recomputed by this one thread (cheap, keeps the reduction single-pass)
             float dm;
             const float oy = out_of(y, row[y], dm);
             a.row_loss[b] = (1.f - a.ls) * (lse - oy) + a.ls * (lse - O / (float)a.C);
         }
     }
+    if (!a.G) return;
     __syncthreads();
-    const float lse = s_lse;
+    lse = s_lse;
     const float k = a.gscale / (float)a.B * a.scale;
     const float qoff = a.ls / (float)a.C;
     float* g = a.G + (size_t)b * a.C;
@@ -220,7 +160,40 @@ __global__ __launch_bounds__(256) void col_normalize_bwd_kernel(const float* W, 
     }
 }
 
+// the rows kernel, and the mean of its row losses when a loss scalar is asked for
+int launch_aam_rows(vp_ctx* ctx, const float* logits, const int64_t* labels, const float* cinv, int B, int C, float margin, float scale,
+                    float ls, int easy, float gscale, float* G, float* loss, float* row_loss, hipStream_t st) {
+    AamBwdArgs a;
+    a.logits = logits; a.labels = (const long long*)labels; a.cinv = cinv; a.G = G; a.row_loss = loss ? row_loss : nullptr;
+    a.B = B; a.C = C; a.mg = vp_margin_of(margin);
+    a.scale = scale; a.ls = ls; a.gscale = gscale; a.easy = easy; a.mt = ctx->margin_table;
+    hipLaunchKernelGGL(aam_ce_bwd_rows_kernel, dim3(B), dim3(256), 0, st, a);
+    VP_LAUNCH_CHECK(ctx, "aam_ce_bwd_rows");
+    return loss ? vp_reduce_rows(ctx, row_loss, B, 1, loss, st) : VP_OK;
+}
+
+// demb (B, D), dW (D, C) from G = d loss / d cos * cinv (B, C): d xn = G W^T, d wn' = xn^T G, then the two normalize-backwards
+int cosine_bwd_tail(vp_ctx* ctx, const float* emb, const float* W, const float* G, const float* rinv, const float* cinv, int B, int D,
+                    int C, float* dxn, float* xnT, float* dwn, float* demb, float* dW, hipStream_t st) {
+    int rc;
+    if ((rc = vp_dense_f32_ex(ctx, G, C, W, /*w_is_kn=*/0, nullptr, nullptr, nullptr, B, D, C, VP_ACT_NONE, dxn, D, st))) return rc;
+    hipLaunchKernelGGL(transpose_scale_kernel, dim3((B * D + 255) / 256), dim3(256), 0, st, emb, rinv, B, D, xnT);
+    VP_LAUNCH_CHECK(ctx, "transpose_scale");
+    if ((rc = vp_dense_f32_ex(ctx, xnT, B, G, /*w_is_kn=*/1, nullptr, nullptr, nullptr, D, C, B, VP_ACT_NONE, dwn, C, st))) return rc;
+    hipLaunchKernelGGL(row_normalize_bwd_kernel, dim3((B + 3) / 4), dim3(256), 0, st, emb, dxn, rinv, B, D, demb);
+    VP_LAUNCH_CHECK(ctx, "row_normalize_bwd");
+    hipLaunchKernelGGL(col_normalize_bwd_kernel, dim3((C + 63) / 64), dim3(256), 0, st, W, dwn, cinv, D, C, dW);
+    VP_LAUNCH_CHECK(ctx, "col_normalize_bwd");
+    return VP_OK;
+}
+
 }  // namespace
+
+int vp_reduce_rows(vp_ctx* ctx, const float* v, int n, int mean, float* out, hipStream_t st) {
+    hipLaunchKernelGGL(reduce_rows_kernel, dim3(1), dim3(256), 0, st, v, n, mean, out);
+    VP_LAUNCH_CHECK(ctx, "reduce_rows");
+    return VP_OK;
+}
 
 extern "C" {
 
@@ -246,17 +219,8 @@ int vp_cosine_logits_f32(vp_ctx* ctx, const float* emb, const float* W, int B, i
 int vp_aam_ce_fwd(vp_ctx* ctx, const float* logits, const int64_t* labels, int B, int C, float margin, float scale,
                   float label_smoothing, int easy_margin, float* loss, float* row_loss, vp_stream stream) {
     if (!ctx || !logits || !labels || !loss || !row_loss || B <= 0 || C <= 0) VP_FAIL(ctx, VP_EINVAL, "aam_ce: bad arguments");
-    hipStream_t st = (hipStream_t)stream;
-    AamArgs a;
-    a.logits = logits; a.labels = (const long long*)labels; a.row_loss = row_loss; a.B = B; a.C = C;
-    a.cos_m = (float)cos((double)margin); a.sin_m = (float)sin((double)margin);
-    a.th = (float)cos(M_PI - (double)margin); a.mmm = (float)(1.0 + cos(M_PI - (double)margin));
-    a.scale = scale; a.ls = label_smoothing; a.easy = easy_margin; a.mt = ctx->margin_table;
-    hipLaunchKernelGGL(aam_ce_rows_kernel, dim3(B), dim3(256), 0, st, a);
-    VP_LAUNCH_CHECK(ctx, "aam_ce_rows");
-    hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(256), 0, st, row_loss, B, loss);
-    VP_LAUNCH_CHECK(ctx, "mean");
-    return VP_OK;
+    return launch_aam_rows(ctx, logits, labels, nullptr, B, C, margin, scale, label_smoothing, easy_margin, 0.f, nullptr, loss, row_loss,
+                           (hipStream_t)stream);
 }
 
 size_t vp_cosine_aam_workspace_bytes(int B, int D, int C) {
@@ -299,28 +263,9 @@ int vp_cosine_aam_ce_bwd(vp_ctx* ctx, const float* emb, const float* W, const in
     float* row_loss = (float*)p;
     int rc = vp_cosine_logits_f32(ctx, emb, W, B, D, C, cosv, ws, lw, stream);
     if (rc) return rc;
-    AamBwdArgs a;
-    a.logits = cosv; a.labels = (const long long*)labels; a.cinv = cinv; a.G = G; a.row_loss = loss ? row_loss : nullptr;
-    a.B = B; a.C = C;
-    a.cos_m = (float)cos((double)margin); a.sin_m = (float)sin((double)margin);
-    a.th = (float)cos(M_PI - (double)margin); a.mmm = (float)(1.0 + cos(M_PI - (double)margin));
-    a.scale = scale; a.ls = label_smoothing; a.gscale = grad_scale; a.easy = easy_margin; a.mt = ctx->margin_table;
-    hipLaunchKernelGGL(aam_ce_bwd_rows_kernel, dim3(B), dim3(256), 0, st, a);
-    VP_LAUNCH_CHECK(ctx, "aam_ce_bwd_rows");
-    if (loss) {
-        hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(256), 0, st, row_loss, B, loss);
-        VP_LAUNCH_CHECK(ctx, "mean");
-    }
-    // d xn = (G cinv) W^T;  d wn' = xn^T (G cinv)
-    if ((rc = vp_dense_f32_ex(ctx, G, C, W, /*w_is_kn=*/0, nullptr, nullptr, nullptr, B, D, C, VP_ACT_NONE, dxn, D, st))) return rc;
-    hipLaunchKernelGGL(transpose_scale_kernel, dim3((B * D + 255) / 256), dim3(256), 0, st, emb, rinv, B, D, xnT);
-    VP_LAUNCH_CHECK(ctx, "transpose_scale");
-    if ((rc = vp_dense_f32_ex(ctx, xnT, B, G, /*w_is_kn=*/1, nullptr, nullptr, nullptr, D, C, B, VP_ACT_NONE, dwn, C, st))) return rc;
-    hipLaunchKernelGGL(row_normalize_bwd_kernel, dim3((B + 3) / 4), dim3(256), 0, st, emb, dxn, rinv, B, D, demb);
-    VP_LAUNCH_CHECK(ctx, "row_normalize_bwd");
-    hipLaunchKernelGGL(col_normalize_bwd_kernel, dim3((C + 63) / 64), dim3(256), 0, st, W, dwn, cinv, D, C, dW);
-    VP_LAUNCH_CHECK(ctx, "col_normalize_bwd");
-    return VP_OK;
+    if ((rc = launch_aam_rows(ctx, cosv, labels, cinv, B, C, margin, scale, label_smoothing, easy_margin, grad_scale, G, loss, row_loss, st)))
+        return rc;
+    return cosine_bwd_tail(ctx, emb, W, G, rinv, cinv, B, D, C, dxn, xnT, dwn, demb, dW, st);
 }
 
 // Backward of AAMLoss alone (aamloss.py:28-47): dlogits (B, C) = grad_scale * d loss / d cos.  loss (1) optional.
@@ -328,20 +273,8 @@ int vp_aam_ce_bwd(vp_ctx* ctx, const float* logits, const int64_t* labels, int B
                   float label_smoothing, int easy_margin, float grad_scale, float* dlogits, float* loss, float* row_loss,
                   vp_stream stream) {
     if (!ctx || !logits || !labels || !dlogits || B <= 0 || C <= 0 || (loss && !row_loss)) VP_FAIL(ctx, VP_EINVAL, "aam_ce_bwd: bad arguments");
-    hipStream_t st = (hipStream_t)stream;
-    AamBwdArgs a;
-    a.logits = logits; a.labels = (const long long*)labels; a.cinv = nullptr; a.G = dlogits; a.row_loss = loss ? row_loss : nullptr;
-    a.B = B; a.C = C;
-    a.cos_m = (float)cos((double)margin); a.sin_m = (float)sin((double)margin);
-    a.th = (float)cos(M_PI - (double)margin); a.mmm = (float)(1.0 + cos(M_PI - (double)margin));
-    a.scale = scale; a.ls = label_smoothing; a.gscale = grad_scale; a.easy = easy_margin; a.mt = ctx->margin_table;
-    hipLaunchKernelGGL(aam_ce_bwd_rows_kernel, dim3(B), dim3(256), 0, st, a);
-    VP_LAUNCH_CHECK(ctx, "aam_ce_bwd_rows");
-    if (loss) {
-        hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(256), 0, st, row_loss, B, loss);
-        VP_LAUNCH_CHECK(ctx, "mean");
-    }
-    return VP_OK;
+    return launch_aam_rows(ctx, logits, labels, nullptr, B, C, margin, scale, label_smoothing, easy_margin, grad_scale, dlogits, loss,
+                           row_loss, (hipStream_t)stream);
 }
 
 size_t vp_cosine_logits_bwd_workspace_bytes(int B, int D, int C) {
@@ -372,15 +305,7 @@ int vp_cosine_logits_bwd(vp_ctx* ctx, const float* emb, const float* W, const fl
     if (blocks > 256 * 64) blocks = 256 * 64;
     hipLaunchKernelGGL(scale_cols_kernel, dim3((unsigned)blocks), dim3(256), 0, st, dcos, cinv, n, C, G);
     VP_LAUNCH_CHECK(ctx, "scale_cols");
-    if ((rc = vp_dense_f32_ex(ctx, G, C, W, /*w_is_kn=*/0, nullptr, nullptr, nullptr, B, D, C, VP_ACT_NONE, dxn, D, st))) return rc;
-    hipLaunchKernelGGL(transpose_scale_kernel, dim3((B * D + 255) / 256), dim3(256), 0, st, emb, rinv, B, D, xnT);
-    VP_LAUNCH_CHECK(ctx, "transpose_scale");
-    if ((rc = vp_dense_f32_ex(ctx, xnT, B, G, /*w_is_kn=*/1, nullptr, nullptr, nullptr, D, C, B, VP_ACT_NONE, dwn, C, st))) return rc;
-    hipLaunchKernelGGL(row_normalize_bwd_kernel, dim3((B + 3) / 4), dim3(256), 0, st, emb, dxn, rinv, B, D, demb);
-    VP_LAUNCH_CHECK(ctx, "row_normalize_bwd");
-    hipLaunchKernelGGL(col_normalize_bwd_kernel, dim3((C + 63) / 64), dim3(256), 0, st, W, dwn, cinv, D, C, dW);
-    VP_LAUNCH_CHECK(ctx, "col_normalize_bwd");
-    return VP_OK;
+    return cosine_bwd_tail(ctx, emb, W, G, rinv, cinv, B, D, C, dxn, xnT, dwn, demb, dW, st);
 }
 
 size_t vp_cosine_scores_workspace_bytes(int Na, int Nb, int D) {

@@ -8,9 +8,9 @@
 //   per block of 64 utterances: embeddings -> LDS (+ row norms), cos = (E W) * rinv * cinv on the f32 matrix cores
 //   (v_mfma_f32_16x16x4_f32: the exact-f32 arithmetic of the unfused path), margin on the target column, scale, and the block's
 //   per-row online-softmax partials (max, sum exp, sum of logits) over its 64 classes -> part[3][B][tiles].
-// A second small kernel merges the partials per row (log-sum-exp, label smoothing) and a third takes the mean.
+// A second small kernel merges the partials per row (log-sum-exp, label smoothing) and vp_reduce_rows takes the mean.
 // Roofline: f32 MFMA (2 B C D flops at 157 TFLOP/s) for large B, else HBM (4 D C bytes of W); 128 x 200 000 x 192: 9.8 GFLOP = 63 us.
-#include "common.h"
+#include "head_common.h"
 
 #include <math.h>
 
@@ -30,8 +30,8 @@ struct HeadTileArgs {
     float* cinv;                     // [C] column inverse norms (by-product; NULL = not wanted)
     const float* rinv;               // [B] row inverse norms of the embeddings (vp_row_inv_norm ahead of the launch)
     int B, D, C, tiles, SE;          // SE = D + 2
-    float cos_m, sin_m, th, mmm, scale; int easy;
-    const float* mt;
+    VpMargin mg; float scale; int easy;
+    const float* mt;                 // device margin table (vp_set_margin_table) or NULL
 };
 
 // sum / max over the 16 lanes of a DPP row; every lane ends with the result
@@ -129,7 +129,7 @@ __global__ __launch_bounds__(256, 2) void head_tile_fwd_kernel(HeadTileArgs a) {
     float* rinv_s = cinv_s + HT_CT;                               // [HT_RF]
     float* red = rinv_s + HT_RF;                                  // [5][4 waves][HT_RF rows] (and [4][64] / [8][HT_RF] for the norms)
     int* lab_s = reinterpret_cast<int*>(red + 5 * 4 * HT_RF);     // [HT_RF] labels of the row block (-1 past B)
-    if (a.mt) { a.cos_m = a.mt[1]; a.sin_m = a.mt[2]; a.th = a.mt[3]; a.mmm = a.mt[4]; }
+    vp_margin_override(a.mg, a.mt, false);
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int li = lane & 15, g = lane >> 4;
     const int tile = blockIdx.x, c0 = tile * HT_CT;
@@ -201,11 +201,7 @@ __global__ __launch_bounds__(256, 2) void head_tile_fwd_kernel(HeadTileArgs a) {
                 const int y = lab_s[row];
                 const float cs = acc[mi][r] * rinv_s[row] * ci;
                 float o = cs;
-                if (c == y) {
-                    const float sine = sqrtf(fmaxf(1.f - cs * cs, 0.f));
-                    const float phi = cs * a.cos_m - sine * a.sin_m;
-                    o = a.easy ? (cs > 0.f ? phi : cs) : (cs > a.th ? phi : cs - a.mmm);
-                }
+                if (c == y) o = vp_aam_margin(a.mg, a.easy, cs);
                 o *= a.scale;
                 if (c == y) a.tgt[b] = o;
                 const float ov = cvalid ? o : -INFINITY;
@@ -273,19 +269,9 @@ __global__ __launch_bounds__(256) void head_tile_merge_kernel(const float* part,
     const float wbc = vp_wave_max(bc);
     const float wbi = -vp_wave_max(bc == wbc ? -bi : -INFINITY);
     if (lane == 0) { sm[3][wv] = wbc; sm[4][wv] = wbi; }
-    const float wmx = vp_wave_max(mx);
-    se = vp_wave_sum(mx == -INFINITY ? 0.f : se * expf(mx - wmx));
-    so = vp_wave_sum(so);
-    if (lane == 0) { sm[0][wv] = wmx; sm[1][wv] = se; sm[2][wv] = so; }
-    __syncthreads();
+    float lse, O;
+    vp_lse_merge(mx, se, so, sm, lse, O);                        // rows 0 .. 2 of sm
     if (tid == 0) {
-        const float M = fmaxf(fmaxf(sm[0][0], sm[0][1]), fmaxf(sm[0][2], sm[0][3]));
-        float S = 0.f, O = 0.f;
-        for (int w = 0; w < 4; ++w) {
-            S += (sm[0][w] == -INFINITY) ? 0.f : sm[1][w] * expf(sm[0][w] - M);
-            O += sm[2][w];
-        }
-        const float lse = M + logf(S);
         if (lse_out) lse_out[b] = lse;
         row_loss[b] = (1.f - ls) * (lse - tgt[b]) + ls * (lse - O / (float)C);
         if (pred) {
@@ -296,17 +282,6 @@ __global__ __launch_bounds__(256) void head_tile_merge_kernel(const float* part,
         }
     }
 }
-
-__global__ __launch_bounds__(256) void head_mean_kernel(const float* v, int n, float* out) {
-    __shared__ float sm[4];
-    float s = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) s += v[i];
-    s = vp_wave_sum(s);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) out[0] = (sm[0] + sm[1] + sm[2] + sm[3]) / (float)n;
-}
-
 
 // ------------------------------------------------------------------------------------------------ backward, class-tiled
 // d loss / d emb and d loss / d W without the (B, C) cosine and gradient matrices (unfused: both are written and re-read, 2 x 102 MB
@@ -326,7 +301,7 @@ struct HeadBwdArgs {
     const float* emb; const float* W; const long long* labels; const float* lse;
     float* dW; float* dxn_part;      // [gridDim.x][B][D]
     int B, D, C, tiles, SE;
-    float cos_m, sin_m, th, mmm, scale, ls, gscale; int easy;
+    VpMargin mg; float scale, ls, gscale; int easy;
     const float* mt;
 };
 
@@ -344,7 +319,7 @@ __global__ __launch_bounds__(256) void head_tile_bwd_kernel(HeadBwdArgs a) {
     float* lse_s = rinv_s + HT_RB;                                // [64]
     float* red = lse_s + HT_RB;                                   // [4][64]
     int* lab_s = reinterpret_cast<int*>(red + 4 * 64);            // [64]
-    if (a.mt) { a.cos_m = a.mt[1]; a.sin_m = a.mt[2]; a.th = a.mt[3]; a.mmm = a.mt[4]; }
+    vp_margin_override(a.mg, a.mt, false);
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int li = lane & 15, g = lane >> 4;
     const int cw = wv * 16;
@@ -429,13 +404,7 @@ __global__ __launch_bounds__(256) void head_tile_bwd_kernel(HeadBwdArgs a) {
                             const int y = lab_s[row];
                             const float cs = acc[mi][r] * rinv_s[row] * ci;
                             float o = cs, dm = 1.f;
-                            if (c == y) {
-                                const float sine = sqrtf(fmaxf(1.f - cs * cs, 0.f));
-                                const float phi = cs * a.cos_m - sine * a.sin_m;
-                                const bool use_phi = a.easy ? (cs > 0.f) : (cs > a.th);
-                                o = use_phi ? phi : (a.easy ? cs : cs - a.mmm);
-                                if (use_phi) dm = a.cos_m + cs * a.sin_m / sine;
-                            }
+                            if (c == y) o = vp_aam_margin(a.mg, a.easy, cs, dm);
                             o *= a.scale;
                             const float q = qoff + (c == y ? 1.f - a.ls : 0.f);
                             const float gv = (cvalid && y >= 0) ? kk * (expf(o - lse_s[row]) - q) * dm * ci : 0.f;
@@ -565,8 +534,7 @@ int vp_cosine_aam_tiled_fwd(vp_ctx* ctx, const float* emb, const float* W, const
     { const int rc = vp_row_inv_norm(ctx, emb, B, D, D, 1e-12f, rinv, st); if (rc != VP_OK) return rc; }
     a.rinv = rinv;
     a.B = B; a.D = D; a.C = C; a.SE = D + 2;
-    a.cos_m = (float)cos((double)margin); a.sin_m = (float)sin((double)margin);
-    a.th = (float)cos(M_PI - (double)margin); a.mmm = (float)(1.0 + cos(M_PI - (double)margin));
+    a.mg = vp_margin_of(margin);
     a.scale = scale; a.easy = easy_margin; a.mt = ctx->margin_table;
     const int smem = (D * HT_SW + HT_RF * (D + 2) + HT_CT + HT_RF + 5 * 4 * HT_RF + HT_RF) * 4;
     static bool attr_set[64] = {};                                 // the attribute is per DEVICE: a process that drives several GPUs sets it on each
@@ -583,9 +551,7 @@ int vp_cosine_aam_tiled_fwd(vp_ctx* ctx, const float* emb, const float* W, const
     VP_LAUNCH_CHECK(ctx, "head_tile_fwd");
     hipLaunchKernelGGL(head_tile_merge_kernel, dim3(B), dim3(256), 0, st, a.part, a.tgt, B, C, a.tiles, label_smoothing, lse, row_loss, pred);
     VP_LAUNCH_CHECK(ctx, "head_tile_merge");
-    hipLaunchKernelGGL(head_mean_kernel, dim3(1), dim3(256), 0, st, row_loss, B, loss);
-    VP_LAUNCH_CHECK(ctx, "head_mean");
-    return VP_OK;
+    return vp_reduce_rows(ctx, row_loss, B, 1, loss, st);
 }
 
 size_t vp_cosine_aam_tiled_bwd_workspace_bytes(int B, int D, int C) {
@@ -617,8 +583,7 @@ int vp_cosine_aam_tiled_bwd(vp_ctx* ctx, const float* emb, const float* W, const
     HeadBwdArgs a;
     a.emb = emb; a.W = W; a.labels = (const long long*)labels; a.lse = lse; a.dW = dW; a.dxn_part = part;
     a.B = B; a.D = D; a.C = C; a.tiles = (C + HT_CT - 1) / HT_CT; a.SE = D + 2;
-    a.cos_m = (float)cos((double)margin); a.sin_m = (float)sin((double)margin);
-    a.th = (float)cos(M_PI - (double)margin); a.mmm = (float)(1.0 + cos(M_PI - (double)margin));
+    a.mg = vp_margin_of(margin);
     a.scale = scale; a.ls = label_smoothing; a.gscale = grad_scale; a.easy = easy_margin; a.mt = ctx->margin_table;
     const int nwg = a.tiles < 256 ? a.tiles : 256;
     const int smem = (D * HT_SW + HT_RB * (D + 2) + HT_RB * HT_SG + 64 * 3 + 4 * 64 + 64) * 4;

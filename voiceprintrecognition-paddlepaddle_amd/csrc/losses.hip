@@ -11,7 +11,7 @@
 // followed by CrossEntropyLoss(label_smoothing) with mean (or sum / B) reduction.  One workgroup per utterance walks its
 // logits row twice: online log-sum-exp, then the gradient.  No one-hot / margin / prediction tensors exist (the reference
 // builds three to six (B, C) temporaries and fills the margin with a Python loop over the batch).  Reductions are fixed-order.
-#include "common.h"
+#include "head_common.h"
 
 #include <math.h>
 
@@ -20,7 +20,7 @@ namespace {
 struct MarginArgs {
     const float* logits; const long long* labels; float* G; float* row_loss;
     int B, C, K, kind, easy;
-    float cos_m, sin_m, th, mmm, margin, scale, ls, gscale;
+    VpMargin mg; float scale, ls, gscale;      // mg.m: the margin of AM / ARM (0 for the other kinds)
     const float* mt;                 // device margin table (vp_set_margin_table) or NULL
 };
 
@@ -38,63 +38,45 @@ __device__ __forceinline__ float class_value(const float* row, int c, int K, int
 // the logit that enters the softmax and its derivative w.r.t. the class value; zy = scaled target logit (ARM only)
 __device__ __forceinline__ float margin_out(const MarginArgs& a, bool target, float v, float zy, float& dm) {
     switch (a.kind) {
-    case VP_LOSS_AM: dm = a.scale; return a.scale * (target ? v - a.margin : v);
+    case VP_LOSS_AM: dm = a.scale; return a.scale * (target ? v - a.mg.m : v);
     case VP_LOSS_ARM: {
-        const float z = a.scale * (target ? v - a.margin : v);
+        const float z = a.scale * (target ? v - a.mg.m : v);
         if (z - zy < 0.f) { dm = 0.f; return 0.f; }
         dm = a.scale;
         return z;
     }
     case VP_LOSS_CE: dm = 1.f; return v;
     default: {                                                       // VP_LOSS_AAM, VP_LOSS_SUBCENTER
-        float o = v;
-        dm = a.scale;
-        if (target) {
-            const float sine = sqrtf(fmaxf(1.f - v * v, 0.f));
-            const float phi = v * a.cos_m - sine * a.sin_m;
-            const bool use_phi = a.easy ? (v > 0.f) : (v > a.th);
-            o = use_phi ? phi : (a.easy ? v : v - a.mmm);
-            if (use_phi) dm = a.scale * (a.cos_m + v * a.sin_m / sine);
-        }
+        float o = v, d = 1.f;
+        if (target) o = vp_aam_margin(a.mg, a.easy, v, d);
+        dm = a.scale * d;
         return o * a.scale;
     }
     }
 }
 
+// Kind AAM with K = 1 is the arithmetic of aam_ce_bwd_rows_kernel (head.hip) but not its bits: this kernel folds scale into dm, that one
+// into k, and that one carries cinv -- the two stay apart.
 __global__ __launch_bounds__(256) void margin_ce_rows_kernel(MarginArgs a) {
     __shared__ float sm[3][4];
     __shared__ float s_lse;
-    if (a.mt) {
-        a.cos_m = a.mt[1]; a.sin_m = a.mt[2]; a.th = a.mt[3]; a.mmm = a.mt[4];
-        if (a.kind == VP_LOSS_AM || a.kind == VP_LOSS_ARM) a.margin = a.mt[0];
-    }
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    vp_margin_override(a.mg, a.mt, a.kind == VP_LOSS_AM || a.kind == VP_LOSS_ARM);
+    const int b = blockIdx.x, tid = threadIdx.x;
     const float* row = a.logits + (size_t)b * a.C * a.K;
     const int y = (int)a.labels[b];
     int arg;
     const float vy = class_value(row, y, a.K, arg);
-    const float zy = a.scale * (vy - a.margin);
+    const float zy = a.scale * (vy - a.mg.m);
     float mx = -INFINITY, se = 0.f, so = 0.f;
     for (int c = tid; c < a.C; c += 256) {
         float dm;
         const float o = margin_out(a, c == y, class_value(row, c, a.K, arg), zy, dm);
         so += o;
-        if (o > mx) { se = se * expf(mx - o) + 1.f; mx = o; }
-        else se += expf(o - mx);
+        vp_lse_step(o, mx, se);
     }
-    const float wmx = vp_wave_max(mx);
-    se = vp_wave_sum(mx == -INFINITY ? 0.f : se * expf(mx - wmx));
-    so = vp_wave_sum(so);
-    if (lane == 0) { sm[0][wv] = wmx; sm[1][wv] = se; sm[2][wv] = so; }
-    __syncthreads();
+    float lse, O;
+    vp_lse_merge(mx, se, so, sm, lse, O);
     if (tid == 0) {
-        const float M = fmaxf(fmaxf(sm[0][0], sm[0][1]), fmaxf(sm[0][2], sm[0][3]));
-        float S = 0.f, O = 0.f;
-        for (int w = 0; w < 4; ++w) {
-            S += (sm[0][w] == -INFINITY) ? 0.f : sm[1][w] * expf(sm[0][w] - M);
-            O += sm[2][w];
-        }
-        const float lse = M + logf(S);
         s_lse = lse;
         if (a.row_loss) {
             float dm;
@@ -104,7 +86,7 @@ __global__ __launch_bounds__(256) void margin_ce_rows_kernel(MarginArgs a) {
     }
     if (!a.G) return;
     __syncthreads();
-    const float lse = s_lse;
+    lse = s_lse;
     const float k = a.gscale / (float)a.B;
     const float qoff = a.ls / (float)a.C;
     float* g = a.G + (size_t)b * a.C * a.K;
@@ -120,7 +102,7 @@ __global__ __launch_bounds__(256) void margin_ce_rows_kernel(MarginArgs a) {
 struct SphereArgs {
     const float* logits; const long long* labels; const float* bias; float* G; float* row_loss; float* row_dbias;
     int B, C, t, type_a;
-    float cos_m, sin_m, th, mmm, margin, scale, lam, gscale;
+    VpMargin mg; float scale, lam, gscale;
     const float* mt;
 };
 
@@ -140,15 +122,12 @@ __device__ __forceinline__ float fun_g(float z, int t, float& dg) {
 __device__ __forceinline__ float sphere_term(const SphereArgs& a, bool target, float cs, float bias, float& dcos, float& dbias) {
     float z = cs, dz = 1.f;
     if (a.type_a) {
-        const float sn = sqrtf(fmaxf(1.f - cs * cs, 0.f));
-        if (target) {
-            if (cs > a.th) { z = cs * a.cos_m - sn * a.sin_m; dz = a.cos_m + cs * a.sin_m / sn; }
-            else z = cs - a.mmm;
-        } else { z = cs * a.cos_m + sn * a.sin_m; dz = a.cos_m - cs * a.sin_m / sn; }
+        if (target) z = vp_aam_margin(a.mg, /*easy=*/0, cs, dz);
+        else { const float sn = vp_clamped_sine(cs); z = cs * a.mg.cos_m + sn * a.mg.sin_m; dz = a.mg.cos_m - cs * a.mg.sin_m / sn; }
     }
     float dg;
     float gz = fun_g(z, a.t, dg);
-    if (!a.type_a) gz += target ? -a.margin : a.margin;
+    if (!a.type_a) gz += target ? -a.mg.m : a.mg.m;
     const float x = a.scale * gz + bias;
     if (target) {
         dbias = -a.lam * sigmoidf(-x);
@@ -162,7 +141,7 @@ __device__ __forceinline__ float sphere_term(const SphereArgs& a, bool target, f
 
 __global__ __launch_bounds__(256) void sphereface2_rows_kernel(SphereArgs a) {
     __shared__ float sm[2][4];
-    if (a.mt) { a.margin = a.mt[0]; a.cos_m = a.mt[1]; a.sin_m = a.mt[2]; a.th = a.mt[3]; a.mmm = a.mt[4]; }
+    vp_margin_override(a.mg, a.mt, true);
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const float* row = a.logits + (size_t)b * a.C;
     const int y = (int)a.labels[b];
@@ -185,34 +164,18 @@ __global__ __launch_bounds__(256) void sphereface2_rows_kernel(SphereArgs a) {
     }
 }
 
-// out[0] = (mean ? 1 / n : 1) * sum v, fixed order
-__global__ __launch_bounds__(256) void reduce_rows_kernel(const float* v, int n, int mean, float* out) {
-    __shared__ float sm[4];
-    float s = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) s += v[i];
-    s = vp_wave_sum(s);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) out[0] = (sm[0] + sm[1] + sm[2] + sm[3]) * (mean ? 1.f / (float)n : 1.f);
-}
-
 int launch_margin(vp_ctx* ctx, const float* logits, const int64_t* labels, int B, int C, int K, int kind, float margin, float scale,
                   float ls, int easy, float gscale, float* G, float* loss, float* row_loss, hipStream_t st) {
     MarginArgs a;
     a.logits = logits; a.labels = (const long long*)labels; a.G = G; a.row_loss = row_loss;
     a.B = B; a.C = C; a.K = K; a.kind = kind; a.easy = easy;
-    a.cos_m = (float)cos((double)margin); a.sin_m = (float)sin((double)margin);
-    a.th = (float)cos(M_PI - (double)margin); a.mmm = (float)(1.0 + cos(M_PI - (double)margin));
-    a.margin = (kind == VP_LOSS_AM || kind == VP_LOSS_ARM) ? margin : 0.f;
+    a.mg = vp_margin_of(margin);
+    if (kind != VP_LOSS_AM && kind != VP_LOSS_ARM) a.mg.m = 0.f;
     a.scale = kind == VP_LOSS_CE ? 1.f : scale;
     a.ls = ls; a.gscale = gscale; a.mt = ctx->margin_table;
     hipLaunchKernelGGL(margin_ce_rows_kernel, dim3(B), dim3(256), 0, st, a);
     VP_LAUNCH_CHECK(ctx, "margin_ce_rows");
-    if (loss) {
-        hipLaunchKernelGGL(reduce_rows_kernel, dim3(1), dim3(256), 0, st, row_loss, B, 1, loss);
-        VP_LAUNCH_CHECK(ctx, "reduce_rows");
-    }
-    return VP_OK;
+    return loss ? vp_reduce_rows(ctx, row_loss, B, 1, loss, st) : VP_OK;
 }
 
 bool margin_args_ok(const float* logits, const int64_t* labels, int B, int C, int K, int kind) {
@@ -251,18 +214,11 @@ int vp_sphereface2(vp_ctx* ctx, const float* logits, const int64_t* labels, cons
     a.logits = logits; a.labels = (const long long*)labels; a.bias = bias; a.G = dlogits; a.row_loss = row_loss;
     a.row_dbias = dbias ? row_dbias : nullptr;
     a.B = B; a.C = C; a.t = t; a.type_a = margin_type_a;
-    a.cos_m = (float)cos((double)margin); a.sin_m = (float)sin((double)margin);
-    a.th = (float)cos(M_PI - (double)margin); a.mmm = (float)(1.0 + cos(M_PI - (double)margin));
-    a.margin = margin; a.scale = scale; a.lam = lanbuda; a.gscale = grad_scale; a.mt = ctx->margin_table;
+    a.mg = vp_margin_of(margin); a.scale = scale; a.lam = lanbuda; a.gscale = grad_scale; a.mt = ctx->margin_table;
     hipLaunchKernelGGL(sphereface2_rows_kernel, dim3(B), dim3(256), 0, st, a);
     VP_LAUNCH_CHECK(ctx, "sphereface2_rows");
-    hipLaunchKernelGGL(reduce_rows_kernel, dim3(1), dim3(256), 0, st, row_loss, B, 1, loss);
-    VP_LAUNCH_CHECK(ctx, "reduce_rows");
-    if (dbias) {
-        hipLaunchKernelGGL(reduce_rows_kernel, dim3(1), dim3(256), 0, st, row_dbias, B, 0, dbias);
-        VP_LAUNCH_CHECK(ctx, "reduce_rows");
-    }
-    return VP_OK;
+    const int rc = vp_reduce_rows(ctx, row_loss, B, 1, loss, st);
+    return rc || !dbias ? rc : vp_reduce_rows(ctx, row_dbias, B, 0, dbias, st);
 }
 
 }  // extern "C"

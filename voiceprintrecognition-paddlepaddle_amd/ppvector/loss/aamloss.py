@@ -3,7 +3,7 @@
 forward(inputs, labels) takes the classifier's dict and returns the scalar mean loss;
 update(margin) is what MarginScheduler calls every step (optimizer/scheduler.py:69,76).  The
 margin / one-hot mix / scale / softmax-CE(label_smoothing) chain is one kernel over the logits
-(csrc/head.hip aam_ce_rows_kernel) -- no one-hot tensor, no (B, C) temporaries.
+(csrc/head.hip aam_ce_bwd_rows_kernel, without its gradient pass) -- no one-hot tensor, no (B, C) temporaries.
 """
 import math
 
