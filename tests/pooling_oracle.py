@@ -8,7 +8,7 @@ context) or [mean | sqrt(var_unbiased + eps)] (TemporalStatsPool), the variance 
 (what torch.std returns).  Every function takes the float64 images of the f32 / bf16 numbers a kernel reads, shaped (B, T, C).
 
 `asp_stats_bwd` / `time_stats_bwd` are float64 autograd; `asp_stats_bwd_closed` / `time_stats_bwd_coeffs` are the closed forms
-written in the comments of csrc/train_ops.hip (tests/test_pooling_oracle_cpu.py holds them to autograd at 1e-12).
+written in the comments of csrc/pooling_stats.hip (tests/test_pooling_oracle_cpu.py holds them to autograd at 1e-12).
 
 `asp_stats_f32_restatement` is NOT a reference: it restates the forward in float32 NumPy in the kernels' order of operations and
 exists to say how far ANY f32 one-pass implementation of that formula lies from float64 -- the forward bound of
@@ -99,7 +99,7 @@ def asp_stats_bwd(e, x, dpooled, eps=EPS):
 
 
 def asp_stats_bwd_closed(e, x, dpooled, eps=EPS):
-    """The closed forms of csrc/train_ops.hip (attn_stats_bwd_kernel's comment), float64:
+    """The closed forms of csrc/pooling_stats.hip (attn_stats_bwd_kernel's comment), float64:
         dv = [var > eps] dsd / (2 sd);  dalpha_t = dmu x_t + dv (x_t - mu)^2;  S = sum_t alpha_t dalpha_t
         de_t = alpha_t (dalpha_t - S);  dx_t = alpha_t (dmu + 2 dv (x_t - mu))"""
     e, x, dp = e.double(), x.double(), dpooled.double()

@@ -341,6 +341,26 @@ def test_time_stats_coefficients_and_bf16_x_on_clamped_channels(N, worst, T):
     assert_constant_channels(c16, got, plus=add.view(c.B, T, C))
 
 
+@pytest.mark.parametrize('T', [7, 161])
+def test_time_stats_bwd_add_f32_in_place(N, worst, T):
+    """vp_time_stats_bwd_add_f32 (the f32 ASP backward with global context; no other test names it): the gradient through the
+    biased statistics added in place to another gradient of x, handed the float64 reference's stats rounded to f32.  The f32 sum
+    add + g rounds at half an ulp of add (~1): 6e-8 against g ~ 2 / T, 5e-6 at T = 161 -- inside the family's 2e-5."""
+    lib, ctx = N.lib(), hctx(N)
+    C = 64
+    c = po.time_case(T, C, False)
+    add = torch.randn(c.B * T, C, generator=torch.Generator().manual_seed(T))
+    out, xd, st, dsd = add.clone().cuda(), rows(c.x), c.stats.float().cuda(), c.ds.cuda()
+    N.check(lib.vp_time_stats_bwd_add_f32(ctx, xd.data_ptr(), C, st.data_ptr(), dsd.data_ptr(), c.B, T, C, 1e-12, 0, out.data_ptr(), C,
+                                          out.data_ptr(), C, N.stream_ptr()), ctx)
+    got = out.cpu().view(c.B, T, C)
+    e_dx = po.rel(got.double() - add.view(c.B, T, C).double(), c.dx)
+    print(f'[time stats add_f32] T={T}: dx {e_dx:.2e}')
+    note(worst, 'vp_time_stats_bwd_add_f32', dx=e_dx)
+    assert torch.isfinite(got).all() and e_dx < 2e-5, e_dx
+    assert_constant_channels(c, got, plus=add.view(c.B, T, C))
+
+
 # ------------------------------------------------------------------------------------------------------------ (g) argument checks
 @pytest.mark.parametrize('bad', ['B = 65536', 'T = 0', 'null pooled'])
 def test_argument_checks(N, bad):

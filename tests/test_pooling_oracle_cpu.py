@@ -17,7 +17,7 @@ def _close(got, ref, tol=1e-12):
 @pytest.mark.parametrize('T,C,r,planted', [(1, 8, 3, False), (2, 8, 3, False), (9, 8, 0, False), (47, 16, 3, False), (37, 16, 3, True),
                                            (333, 8, 10, True)])
 def test_asp_closed_forms_are_float64_autograd(T, C, r, planted):
-    """dv, dalpha, S, de, dx of csrc/train_ops.hip against autograd of the defining graph, intermediate by intermediate."""
+    """dv, dalpha, S, de, dx of csrc/pooling_stats.hip against autograd of the defining graph, intermediate by intermediate."""
     x, e, dp = po.inputs(2, T, C, r, 11 * T + C, planted)
     cf = po.asp_stats_bwd_closed(e, x, dp)
     de, dx = po.asp_stats_bwd(e, x, dp)

@@ -5,6 +5,7 @@ batch.  Run it on two checkouts (each with its own build), then compare the two 
     python tools/engine_bits.py --out DIR            # 36 arrays (+ EcapaTdnn float32x3 says which path ran; VPMI_X3_GENERIC=1 pins the generic one)
     python tools/engine_bits.py --compare DIR_A DIR_B
     python tools/engine_bits.py --heads --out DIR    # instead: every output of the head / loss entry points (csrc/head.hip, head_tiled.hip, losses.hip)
+    python tools/engine_bits.py --pooling --out DIR  # instead: every output of the pooling-statistics entry points (csrc/pooling_stats.hip)
     python tools/engine_bits.py --time-b1            # 200 B = 1 forwards of ECAPA and ResNetSE per engine, GPU events (host launch overhead)
 """
 import argparse
@@ -168,6 +169,108 @@ def dump_heads(out):
         print(f'{cfg}: {count} arrays so far, {blank} of them all-zero or not finite', flush=True)
 
 
+# --pooling: the frame counts of tests/pooling_oracle.py's sweep (both sides of every dispatch edge of csrc/pooling_stats.hip)
+POOL_T = (1, 2, 7, 8, 9, 47, 159, 160, 161, 319, 320, 321, 333)
+POOL_SENTINEL = -768.0        # every output starts as this: an element nobody wrote, or a refused call that wrote, shows in the dump
+
+
+def dump_pooling(out):
+    """Every output array of the sixteen pooling-statistics entry points on seeded inputs (channel 0 constant over time: the clamp holds
+    there).  Low-precision outputs are saved as their bit patterns."""
+    import torch
+    from ppvector import _native as N
+    os.makedirs(out, exist_ok=True)
+    lib, ctx, st = N.lib(), N.ctx(0), N.stream_ptr()
+    bf = torch.bfloat16
+    count = blank = 0
+
+    def rand(seed, *shape, dtype=torch.float32, flat0=False):
+        t = torch.randn(*shape, generator=torch.Generator().manual_seed(seed))
+        if flat0:
+            t[..., 0] = 1.25
+        return t.to(dtype).cuda()
+
+    def buf(*shape, dtype=torch.float32):
+        return torch.full(shape, POOL_SENTINEL, dtype=dtype, device='cuda')
+
+    def save(tag, **arrays):
+        nonlocal count, blank
+        torch.cuda.synchronize()
+        for k, v in arrays.items():
+            np.save(os.path.join(out, f'pooling_{tag}.{k}.npy'), (v.view(torch.int16) if v.dtype == bf else v).cpu().numpy())
+            count += 1
+            blank += not bool(torch.isfinite(v.float()).all()) or bool((v == POOL_SENTINEL).all())
+
+    def ok(rc, refused=False):
+        if refused:
+            assert rc == N.VP_EUNSUP, rc
+        else:
+            N.check(rc, ctx)
+
+    B = 3
+    for l16, x16 in itertools.product((False, True), (False, True)):
+        for C, T, sliced in itertools.product((64, 96 if x16 else 100), POOL_T, (False, True)):
+            # sliced: x is columns [xoff, xoff + C) of a (B*T, ldx) buffer; d x goes to rows lddx apart
+            ldx, xoff, lddx = (C + 32, 16, C + 8) if sliced else (C, 0, C)
+            tag = f'l{16 if l16 else 32}_x{16 if x16 else 32}_C{C}_T{T}' + ('_slice' if sliced else '')
+            e = rand(1000 * T + C, B * T, C, dtype=bf if l16 else torch.float32)
+            x = rand(2000 * T + C, B * T, ldx, dtype=bf if x16 else torch.float32)
+            x[:, xoff] = 1.25
+            xdt, refused = N.VP_BF16 if x16 else N.VP_F32, l16 and T > 320
+            pooled = buf(B, 2 * C)
+            if l16:
+                ok(lib.vp_asp_softmax_stats_l16(ctx, e.data_ptr(), x.data_ptr(), xdt, ldx, xoff, B, T, C, 1e-12, pooled.data_ptr(), st), refused)
+            else:
+                ok(lib.vp_asp_softmax_stats(ctx, xdt, e.data_ptr(), x.data_ptr(), ldx, xoff, B, T, C, 1e-12, pooled.data_ptr(), st))
+            save(f'{tag}_fwd', pooled=pooled)
+            if x16 and not l16:
+                continue                            # (no backward reads bf16 x beside f32 logits)
+            dp, xp = rand(3000 * T + C, B, 2 * C), x.data_ptr() + xoff * x.element_size()
+            for name in ('vp_attn_stats_bwd_e16',) if l16 else ('vp_attn_stats_bwd_f32', 'vp_attn_stats_bwd_de16'):
+                de, dx = buf(B * T, C, dtype=torch.float32 if name.endswith('f32') else bf), buf(B * T, lddx)
+                if l16:
+                    ok(lib.vp_attn_stats_bwd_e16(ctx, e.data_ptr(), xp, xdt, ldx, pooled.data_ptr(), dp.data_ptr(), B, T, C, 1e-12, de.data_ptr(),
+                                                 dx.data_ptr(), lddx, st), refused)
+                else:
+                    ok(getattr(lib, name)(ctx, e.data_ptr(), xp, ldx, pooled.data_ptr(), dp.data_ptr(), B, T, C, 1e-12, de.data_ptr(), dx.data_ptr(),
+                                          lddx, st))
+                save(f'{tag}_{name}', de=de, dx=dx)
+        print(f'attentive, logits {"bf16" if l16 else "f32"}, x {"bf16" if x16 else "f32"}: {count} arrays so far', flush=True)
+
+    for C, T, unbiased in itertools.product((64, 98), (1, 7, 33, 100), (0, 1)):
+        tag, eps = f'C{C}_T{T}_u{unbiased}', 1e-8 if unbiased else 1e-12
+        x, ds = rand(7000 * T + C, B * T, C, flat0=True), rand(8000 * T + C, B, 2 * C)
+        stats, ab = buf(B, 2 * C), buf(2, B, C)
+        ok(lib.vp_time_stats_f32(ctx, x.data_ptr(), C, B, T, C, eps, unbiased, stats.data_ptr(), st))
+        ok(lib.vp_time_stats_bwd_coeffs(ctx, stats.data_ptr(), ds.data_ptr(), B, T, C, eps, ab.data_ptr(), st))
+        save(f'time_{tag}', stats=stats, ab=ab)
+        if C % 4:
+            continue                                # (the backward passes are four channels wide)
+        add, x16 = rand(9000 * T + C, B * T, C), x.to(bf)
+        dx, dxa, dxb = buf(B * T, C), buf(B * T, C), buf(B * T, C)
+        ok(lib.vp_time_stats_bwd_f32(ctx, x.data_ptr(), C, stats.data_ptr(), ds.data_ptr(), B, T, C, eps, unbiased, dx.data_ptr(), C, st))
+        ok(lib.vp_time_stats_bwd_add_f32(ctx, x.data_ptr(), C, stats.data_ptr(), ds.data_ptr(), B, T, C, eps, unbiased, add.data_ptr(), C,
+                                         dxa.data_ptr(), C, st))
+        ok(lib.vp_time_stats_bwd_add_x16(ctx, x16.data_ptr(), C, stats.data_ptr(), ds.data_ptr(), B, T, C, eps, unbiased, add.data_ptr(), C,
+                                         dxb.data_ptr(), C, st))
+        save(f'time_{tag}_bwd', dx=dx, dx_add=dxa, dx_add_x16=dxb)
+    Bw, Tw, Cw = 2, 4000, 64                        # 63 chunks
+    x = rand(11, Bw * Tw, Cw, flat0=True)
+    ws = torch.zeros(lib.vp_time_stats_workspace_bytes(Bw, Tw, Cw), dtype=torch.uint8, device='cuda')
+    for unbiased in (0, 1):
+        stats = buf(Bw, 2 * Cw)
+        ok(lib.vp_time_stats_ws_f32(ctx, x.data_ptr(), Cw, Bw, Tw, Cw, 1e-8 if unbiased else 1e-12, unbiased, stats.data_ptr(), ws.data_ptr(),
+                                    ws.numel(), st))
+        save(f'time_ws_u{unbiased}', stats=stats)
+    for C in (64, 100):
+        a, s32, s16 = rand(13 + C, B * 47, C), buf(B, C), buf(B, C)
+        a16 = a.to(bf)
+        ok(lib.vp_utt_sums_f32(ctx, a.data_ptr(), C, B, 47, C, s32.data_ptr(), st))
+        ok(lib.vp_utt_sums_b16(ctx, a16.data_ptr(), C, B, 47, C, s16.data_ptr(), st))
+        save(f'utt_sums_C{C}', f32=s32, b16=s16)
+    print(f'{count} arrays, {blank} of them untouched or not finite (the refused bf16-logit calls at T > 320 leave theirs untouched)', flush=True)
+
+
 def _ulps(x, y):
     """Largest distance of two f32 arrays in units in the last place (inf where a NaN or the shapes differ)."""
     if x.shape != y.shape or x.dtype != np.float32 or np.isnan(x).any() or np.isnan(y).any():
@@ -226,6 +329,7 @@ if __name__ == '__main__':
     ap.add_argument('--compare', nargs=2)
     ap.add_argument('--time-b1', action='store_true')
     ap.add_argument('--heads', action='store_true')
+    ap.add_argument('--pooling', action='store_true')
     a = ap.parse_args()
     if a.compare:
         sys.exit(1 if compare(*a.compare) else 0)
@@ -233,5 +337,7 @@ if __name__ == '__main__':
         time_b1()
     if a.out and a.heads:
         dump_heads(a.out)
+    elif a.out and a.pooling:
+        dump_pooling(a.out)
     elif a.out:
         dump(a.out, a.only, a.suffix)

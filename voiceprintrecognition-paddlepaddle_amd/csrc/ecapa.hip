@@ -1,5 +1,5 @@
 // Whole-backbone forward (eval mode) for ECAPA-TDNN and TDNN: the launch graph over the kernels in
-// conv_gemm.hip / small_ops.hip.  Host-only code; everything it enqueues is asynchronous on the
+// conv_gemm.hip / small_ops.hip / pooling_stats.hip.  Host-only code; everything it enqueues is asynchronous on the
 // caller's stream and touches only the caller's workspace, so the sequence is hipGraph-capturable.
 //
 // Reference graphs: EcapaTdnn.forward (ppvector/models/ecapa_tdnn.py:245-276) with SERes2NetBlock

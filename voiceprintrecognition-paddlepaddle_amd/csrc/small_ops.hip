@@ -1,5 +1,5 @@
 // Per-utterance (M = batch) pieces of the path: time-moment finalisation, exact-f32 dense layers on
-// the f32 matrix cores, SE gating + residual, attention softmax + weighted statistics.
+// the f32 matrix cores, SE gating + residual (the pooling statistics: pooling_stats.hip).
 // All HBM/L2-bound or tiny; kept in f32 so that they add no error on top of the f32 reference.
 #include "common.h"
 
@@ -311,86 +311,6 @@ __global__ __launch_bounds__(256) void im2col_hl_kernel(Im2colArgs a) {
     }
 }
 
-// ---------------------------------------------------------------- ASP softmax over time + weighted stats
-// pooling.py:114-123: attn = softmax_t(logits); mean = sum attn x; std = sqrt(clip(sum attn (x-mean)^2, eps)).
-// One workgroup = 64 channels of one utterance; the 4 waves split the frames, online softmax per
-// lane, merged through LDS.  x is centred on `center` (the plain time mean; the inference engines) or, with none given, on the
-// utterance's first frame of the channel, to keep the sums well conditioned in f32: raw E[x^2] - E[x]^2 loses (mean / std)^2 of
-// the std's relative precision.  With no centre given the variance comes from a second pass about the mean (docs/pooling_stats.md).
-template <typename T>
-struct AspArgs {
-    const float* logits; const T* x; const float* center; float* pooled;
-    int ldx, xoff, ldc, B, T_, C; float eps;
-};
-
-template <typename T>
-__global__ __launch_bounds__(256) void asp_softmax_stats_kernel(AspArgs<T> a) {
-    __shared__ float sm[4][4][64];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int b = blockIdx.y;
-    const int c = blockIdx.x * 64 + lane;
-    const bool ok = c < a.C;
-    const int cc = ok ? c : 0;
-    const size_t row0 = (size_t)b * a.T_;
-    // no centre given (the training entry points): the utterance's own first frame of the channel, as time_moments4_kernel does
-    const float mu0 = a.center ? a.center[(size_t)b * a.ldc + cc] : vp_to_f32(a.x[row0 * a.ldx + a.xoff + cc]);
-    float mx = -INFINITY, s0 = 0.f, s1 = 0.f, s2 = 0.f;
-    for (int t = wv; t < a.T_; t += 4) {
-        const float e = a.logits[(row0 + t) * a.C + cc];
-        const float xv = vp_to_f32(a.x[(row0 + t) * a.ldx + a.xoff + cc]) - mu0;
-        if (e > mx) {
-            const float f = expf(mx - e);       // exp(-inf) = 0 on the first frame
-            s0 = s0 * f + 1.f; s1 = s1 * f + xv; s2 = s2 * f + xv * xv; mx = e;
-        } else {
-            const float p = expf(e - mx);
-            s0 += p; s1 += p * xv; s2 += p * xv * xv;
-        }
-    }
-    sm[wv][0][lane] = mx; sm[wv][1][lane] = s0; sm[wv][2][lane] = s1; sm[wv][3][lane] = s2;
-    __syncthreads();
-    if (!a.center) {
-        // second pass about the mean just found: sum p (x - mu)^2 has no cancellation left, whatever the softmax weighs (a peaked
-        // one puts mu far from any fixed centre: var << (mu - centre)^2, and s2 / s0 - md^2 loses var's leading digits)
-        const float M = fmaxf(fmaxf(sm[0][0][lane], sm[1][0][lane]), fmaxf(sm[2][0][lane], sm[3][0][lane]));
-        float t0 = 0.f, t1 = 0.f;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const float mw = sm[w][0][lane];
-            const float f = (mw == -INFINITY) ? 0.f : expf(mw - M);
-            t0 += sm[w][1][lane] * f; t1 += sm[w][2][lane] * f;
-        }
-        const float md = t1 / t0;
-        float v = 0.f;
-        for (int t = wv; t < a.T_; t += 4) {
-            const float p = expf(a.logits[(row0 + t) * a.C + cc] - M);
-            const float d = vp_to_f32(a.x[(row0 + t) * a.ldx + a.xoff + cc]) - mu0 - md;
-            v += p * d * d;
-        }
-        sm[wv][3][lane] = v;                    // (the first pass's s2: not read on this path)
-        __syncthreads();
-        if (wv == 0 && ok) {
-            const float var = (sm[0][3][lane] + sm[1][3][lane] + sm[2][3][lane] + sm[3][3][lane]) / t0;
-            a.pooled[(size_t)b * 2 * a.C + c] = mu0 + md;
-            a.pooled[(size_t)b * 2 * a.C + a.C + c] = sqrtf(fmaxf(var, a.eps));
-        }
-        return;
-    }
-    if (wv == 0 && ok) {
-        float M = fmaxf(fmaxf(sm[0][0][lane], sm[1][0][lane]), fmaxf(sm[2][0][lane], sm[3][0][lane]));
-        float t0 = 0.f, t1 = 0.f, t2 = 0.f;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const float mw = sm[w][0][lane];
-            const float f = (mw == -INFINITY) ? 0.f : expf(mw - M);
-            t0 += sm[w][1][lane] * f; t1 += sm[w][2][lane] * f; t2 += sm[w][3][lane] * f;
-        }
-        const float md = t1 / t0;
-        const float var = t2 / t0 - md * md;
-        a.pooled[(size_t)b * 2 * a.C + c] = mu0 + md;
-        a.pooled[(size_t)b * 2 * a.C + a.C + c] = sqrtf(fmaxf(var, a.eps));
-    }
-}
-
 }  // namespace
 
 static int se_scale_residual_impl(vp_ctx* ctx, int dtype, const void* x, int ldx, int xoff, const float* s,
@@ -444,200 +364,6 @@ int vp_im2col_hl32(vp_ctx* ctx, const float* x, int B, int T, int F, int KW, int
     Im2colArgs a{x, (char*)out, T, F, KW, dil, pad, Kp, total};
     hipLaunchKernelGGL(im2col_hl_kernel, dim3((unsigned)nb), dim3(256), 0, st, a);
     VP_LAUNCH_CHECK(ctx, "im2col_hl32");
-    return VP_OK;
-}
-
-// mean / std over time straight from the activations (small T): stats[b] = [mean(C) | sqrt(max(E[(x-m)^2], eps))]
-namespace {
-template <typename T>
-struct TmArgs { const T* x; float* stats; int ldx, Tn, C; float eps; int unbiased; };
-
-template <typename T>
-__global__ __launch_bounds__(256) void time_moments_kernel(TmArgs<T> a) {
-    __shared__ float sm[2][4][64];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int b = blockIdx.y, c = blockIdx.x * 64 + lane;
-    const bool ok = c < a.C;
-    const int cc = ok ? c : 0;
-    const T* xb = a.x + (size_t)b * a.Tn * a.ldx;
-    const float c0 = vp_to_f32(xb[cc]);
-    float s1 = 0.f, s2 = 0.f;
-    for (int t = wv; t < a.Tn; t += 4) {
-        const float v = vp_to_f32(xb[(size_t)t * a.ldx + cc]) - c0;
-        s1 += v; s2 += v * v;
-    }
-    sm[0][wv][lane] = s1; sm[1][wv][lane] = s2;
-    __syncthreads();
-    if (wv == 0 && ok) {
-        const float t1 = sm[0][0][lane] + sm[0][1][lane] + sm[0][2][lane] + sm[0][3][lane];
-        const float t2 = sm[1][0][lane] + sm[1][1][lane] + sm[1][2][lane] + sm[1][3][lane];
-        const float md = t1 / (float)a.Tn;
-        a.stats[(size_t)b * 2 * a.C + c] = c0 + md;
-        // ASP context: sqrt(clip(var_biased, eps)) (pooling.py:97-104); TSTP: sqrt(var_unbiased + eps) (pooling.py:141)
-        const float ss = fmaxf(t2 - (float)a.Tn * md * md, 0.f);
-        a.stats[(size_t)b * 2 * a.C + a.C + c] = a.unbiased ? sqrtf(ss / (float)(a.Tn > 1 ? a.Tn - 1 : 1) + a.eps)
-                                                            : sqrtf(fmaxf(ss / (float)a.Tn, a.eps));
-    }
-}
-
-// f32 activations (the training path), four channels per lane: 32 lanes x 8 frame groups, four frames' loads in flight
-__global__ __launch_bounds__(256) void time_moments4_kernel(TmArgs<float> a) {
-    __shared__ float sm[2][256][4];
-    const int lc = threadIdx.x & 31, rg = threadIdx.x >> 5;
-    const int b = blockIdx.y, c4 = blockIdx.x * 32 + lc;
-    const int C4 = a.C >> 2;
-    const bool ok = c4 < C4;
-    const int c = ok ? c4 * 4 : 0;
-    const float* xb = a.x + (size_t)b * a.Tn * a.ldx + c;
-    float c0[4], s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
-    vp_load4(xb, c0);
-    int t = rg;
-    for (; t + 24 < a.Tn; t += 32) {
-        float v[4][4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) vp_load4(xb + (size_t)(t + 8 * u) * a.ldx, v[u]);
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { const float d = v[u][e] - c0[e]; s1[e] += d; s2[e] += d * d; }
-    }
-    for (; t < a.Tn; t += 8) {
-        float v[4];
-        vp_load4(xb + (size_t)t * a.ldx, v);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { const float d = v[e] - c0[e]; s1[e] += d; s2[e] += d * d; }
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { sm[0][threadIdx.x][e] = s1[e]; sm[1][threadIdx.x][e] = s2[e]; }
-    __syncthreads();
-    if (rg != 0 || !ok) return;
-    float m[4], sd[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        float t1 = 0.f, t2 = 0.f;
-        for (int r = 0; r < 8; ++r) { t1 += sm[0][r * 32 + lc][e]; t2 += sm[1][r * 32 + lc][e]; }
-        const float md = t1 / (float)a.Tn;
-        m[e] = c0[e] + md;
-        const float ss = fmaxf(t2 - (float)a.Tn * md * md, 0.f);
-        sd[e] = a.unbiased ? sqrtf(ss / (float)(a.Tn > 1 ? a.Tn - 1 : 1) + a.eps) : sqrtf(fmaxf(ss / (float)a.Tn, a.eps));
-    }
-    vp_store4(a.stats + (size_t)b * 2 * a.C + c, m);
-    vp_store4(a.stats + (size_t)b * 2 * a.C + a.C + c, sd);
-}
-}  // namespace
-
-namespace {
-// Many positions per utterance (2-D feature maps): the frames are cut into chunks (grid = channel blocks x B x chunks), partial
-// sums of (x - x[first frame]) and its square per chunk, then a finalize over the chunks in order.  part: [B][chunks][2][C].
-struct TmChunkArgs { const float* x; float* part; int ldx, Tn, C, chunks, rows_per_chunk; };
-__global__ __launch_bounds__(256) void time_moments_chunk_kernel(TmChunkArgs a) {
-    __shared__ float sm[2][256][4];
-    const int lc = threadIdx.x & 31, rg = threadIdx.x >> 5;
-    const int b = blockIdx.y, ch = blockIdx.z, c4 = blockIdx.x * 32 + lc;
-    const int C4 = a.C >> 2;
-    const bool ok = c4 < C4;
-    const int c = ok ? c4 * 4 : 0;
-    const float* xb = a.x + (size_t)b * a.Tn * a.ldx + c;
-    const int t0 = ch * a.rows_per_chunk, t1 = min(a.Tn, t0 + a.rows_per_chunk);
-    float c0[4], s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
-    vp_load4(xb, c0);
-    int t = t0 + rg;
-    for (; t + 24 < t1; t += 32) {
-        float v[4][4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) vp_load4(xb + (size_t)(t + 8 * u) * a.ldx, v[u]);
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { const float d = v[u][e] - c0[e]; s1[e] += d; s2[e] += d * d; }
-    }
-    for (; t < t1; t += 8) {
-        float v[4];
-        vp_load4(xb + (size_t)t * a.ldx, v);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { const float d = v[e] - c0[e]; s1[e] += d; s2[e] += d * d; }
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { sm[0][threadIdx.x][e] = s1[e]; sm[1][threadIdx.x][e] = s2[e]; }
-    __syncthreads();
-    if (rg != 0 || !ok) return;
-    float t1s[4], t2s[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        t1s[e] = 0.f; t2s[e] = 0.f;
-        for (int r = 0; r < 8; ++r) { t1s[e] += sm[0][r * 32 + lc][e]; t2s[e] += sm[1][r * 32 + lc][e]; }
-    }
-    float* p = a.part + ((size_t)b * a.chunks + ch) * 2 * a.C;
-    vp_store4(p + c, t1s);
-    vp_store4(p + a.C + c, t2s);
-}
-struct TmFinArgs { const float* x; const float* part; float* stats; int ldx, Tn, C, chunks, unbiased; float eps; };
-__global__ __launch_bounds__(256) void time_moments_fin_kernel(TmFinArgs a) {
-    const int b = blockIdx.y, c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= a.C) return;
-    float t1 = 0.f, t2 = 0.f;
-    for (int ch = 0; ch < a.chunks; ++ch) {
-        const float* p = a.part + ((size_t)b * a.chunks + ch) * 2 * a.C;
-        t1 += p[c]; t2 += p[a.C + c];
-    }
-    const float c0 = a.x[(size_t)b * a.Tn * a.ldx + c];
-    const float md = t1 / (float)a.Tn;
-    a.stats[(size_t)b * 2 * a.C + c] = c0 + md;
-    const float ss = fmaxf(t2 - (float)a.Tn * md * md, 0.f);
-    a.stats[(size_t)b * 2 * a.C + a.C + c] = a.unbiased ? sqrtf(ss / (float)(a.Tn > 1 ? a.Tn - 1 : 1) + a.eps) : sqrtf(fmaxf(ss / (float)a.Tn, a.eps));
-}
-static void tm_geometry(int B, int T, int C, int& chunks, int& rpc) {
-    const int cblocks = (C / 4 + 31) / 32;
-    long long ch = 2048 / ((long long)B * cblocks > 0 ? (long long)B * cblocks : 1);
-    if (ch < 1) ch = 1;
-    long long r = (T + ch - 1) / ch;
-    if (r < 64) r = 64;
-    rpc = (int)r;
-    chunks = (T + rpc - 1) / rpc;
-}
-}  // namespace
-
-extern "C" size_t vp_time_stats_workspace_bytes(int B, int T, int C) {
-    if (B <= 0 || T <= 0 || C <= 0) return 0;
-    int chunks, rpc;
-    tm_geometry(B, T, C, chunks, rpc);
-    return (size_t)B * chunks * 2 * C * sizeof(float) + 256;
-}
-
-// f32 (B, T, C) with MANY frames per utterance (ResNetSE / ERes2Net feature maps as (B, T*F', C)): [mean | std] with the frames spread over
-// ~2048 workgroups.  C % 4 == 0, ldx % 4 == 0, 16-byte aligned; else VP_EUNSUP (callers use vp_time_stats_f32).
-extern "C" int vp_time_stats_ws_f32(vp_ctx* ctx, const float* x, int ldx, int B, int T, int C, float eps, int unbiased, float* stats, void* ws,
-                                    size_t ws_bytes, vp_stream stream) {
-    if (!ctx || !x || !stats || B <= 0 || T <= 0 || C <= 0 || B > 65535) VP_FAIL(ctx, VP_EINVAL, "time_stats_ws: bad arguments");
-    if (((C | ldx) & 3) || ((uintptr_t)x & 15)) return VP_EUNSUP;
-    if (!ws || ws_bytes < vp_time_stats_workspace_bytes(B, T, C)) VP_FAIL(ctx, VP_EWORKSPACE, "time_stats_ws: workspace too small");
-    int chunks, rpc;
-    tm_geometry(B, T, C, chunks, rpc);
-    hipStream_t st = (hipStream_t)stream;
-    TmChunkArgs a{x, (float*)ws, ldx, T, C, chunks, rpc};
-    hipLaunchKernelGGL(time_moments_chunk_kernel, dim3((C / 4 + 31) / 32, B, chunks), dim3(256), 0, st, a);
-    VP_LAUNCH_CHECK(ctx, "time_moments_chunk");
-    TmFinArgs f{x, (const float*)ws, stats, ldx, T, C, chunks, unbiased, eps};
-    hipLaunchKernelGGL(time_moments_fin_kernel, dim3((C + 255) / 256, B), dim3(256), 0, st, f);
-    VP_LAUNCH_CHECK(ctx, "time_moments_fin");
-    return VP_OK;
-}
-
-int vp_time_moments(vp_ctx* ctx, int dtype, const void* x, int ldx, int B, int T, int C, float eps, int unbiased,
-                    float* stats, hipStream_t st) {
-    if (B > 65535) VP_FAIL(ctx, VP_EINVAL, "time_moments: batch too large");
-    dim3 grid((C + 63) / 64, B);
-    if (dtype != VP_BF16 && ((C | ldx) & 3) == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)stats & 15) == 0) {
-        TmArgs<float> a{(const float*)x, stats, ldx, T, C, eps, unbiased};
-        hipLaunchKernelGGL(time_moments4_kernel, dim3((C / 4 + 31) / 32, B), dim3(256), 0, st, a);
-    } else if (dtype == VP_BF16) {
-        TmArgs<bf16_t> a{(const bf16_t*)x, stats, ldx, T, C, eps, unbiased};
-        hipLaunchKernelGGL(time_moments_kernel<bf16_t>, grid, dim3(256), 0, st, a);
-    } else {
-        TmArgs<float> a{(const float*)x, stats, ldx, T, C, eps, unbiased};
-        hipLaunchKernelGGL(time_moments_kernel<float>, grid, dim3(256), 0, st, a);
-    }
-    VP_LAUNCH_CHECK(ctx, "time_moments");
     return VP_OK;
 }
 
@@ -916,132 +642,6 @@ int vp_se_scale_residual(vp_ctx* ctx, int dtype, const void* x, int ldx, int xof
                          const void* res, int ldr, int roff, void* out, int ldo, int ooff,
                          int B, int T, int C, vp_stream stream) {
     return vp_se_scale_residual_ex(ctx, dtype, x, ldx, xoff, s, res, ldr, roff, out, ldo, ooff, B, T, C, 0, (hipStream_t)stream);
-}
-
-}  // extern "C"
-
-namespace {
-// f32 x (the training engine), T <= 8 NT: a thread keeps its share of an utterance's logits and x in registers -- all loads issued up front
-// (the streaming kernel above has two loads in flight per thread and a divergent branch per frame: 4.2 TB/s) -- then max, then the sums.
-// TL: the logits as stored -- float, or bf16 under enable_amp (a.logits reinterpreted: what Paddle's O1 hands the softmax is the bf16
-// output of the logits conv, cast up)
-template <int NT, typename TL = float, typename TX = float>
-__global__ __launch_bounds__(512) void asp_softmax_stats_reg_kernel(AspArgs<float> a) {
-    const TL* __restrict__ lg = reinterpret_cast<const TL*>(a.logits);
-    const TX* __restrict__ xg = reinterpret_cast<const TX*>(a.x);
-    __shared__ float sm[4][8][64];
-    const int lane = threadIdx.x & 63, rg = threadIdx.x >> 6;
-    const int b = blockIdx.y;
-    const int c = blockIdx.x * 64 + lane;
-    const bool ok = c < a.C;
-    const int cc = ok ? c : 0;
-    const size_t row0 = (size_t)b * a.T_;
-    const float mu0 = a.center ? a.center[(size_t)b * a.ldc + cc] : vp_to_f32(xg[row0 * a.ldx + a.xoff + cc]);    // (as in the streaming kernel)
-    float ev[NT], xv[NT];
-#pragma unroll
-    for (int i = 0; i < NT; ++i) {
-        const int t = min(rg + 8 * i, a.T_ - 1);
-        ev[i] = vp_to_f32(lg[(row0 + t) * a.C + cc]);
-        xv[i] = vp_to_f32(xg[(row0 + t) * a.ldx + a.xoff + cc]);
-    }
-    float mx = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < NT; ++i) if (rg + 8 * i < a.T_) mx = fmaxf(mx, ev[i]);
-    sm[0][rg][lane] = mx;
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < 8; ++q) mx = fmaxf(mx, sm[0][q][lane]);
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < NT; ++i) {
-        if (rg + 8 * i < a.T_) {
-            const float p = expf(ev[i] - mx), d = xv[i] - mu0;
-            s0 += p; s1 += p * d; s2 += p * d * d;
-        }
-    }
-    sm[1][rg][lane] = s0; sm[2][rg][lane] = s1; sm[3][rg][lane] = s2;
-    __syncthreads();
-    if (!a.center) {
-        // the variance from a second pass over the registers, about the mean just found (see asp_softmax_stats_kernel)
-        float t0 = 0.f, t1 = 0.f;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) { t0 += sm[1][q][lane]; t1 += sm[2][q][lane]; }
-        const float md = t1 / t0;
-        float v = 0.f;
-#pragma unroll
-        for (int i = 0; i < NT; ++i) {
-            if (rg + 8 * i < a.T_) {
-                const float p = expf(ev[i] - mx), d = xv[i] - mu0 - md;
-                v += p * d * d;
-            }
-        }
-        sm[0][rg][lane] = v;                    // (the maxima were last read before the barrier above)
-        __syncthreads();
-        if (rg == 0 && ok) {
-            float t2 = 0.f;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) t2 += sm[0][q][lane];
-            a.pooled[(size_t)b * 2 * a.C + c] = mu0 + md;
-            a.pooled[(size_t)b * 2 * a.C + a.C + c] = sqrtf(fmaxf(t2 / t0, a.eps));
-        }
-        return;
-    }
-    if (rg == 0 && ok) {
-        float t0 = 0.f, t1 = 0.f, t2 = 0.f;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) { t0 += sm[1][q][lane]; t1 += sm[2][q][lane]; t2 += sm[3][q][lane]; }
-        const float md = t1 / t0;
-        const float var = t2 / t0 - md * md;
-        a.pooled[(size_t)b * 2 * a.C + c] = mu0 + md;
-        a.pooled[(size_t)b * 2 * a.C + a.C + c] = sqrtf(fmaxf(var, a.eps));
-    }
-}
-}  // namespace
-
-int vp_asp_softmax_stats_ex(vp_ctx* ctx, int dtype, const float* logits, const void* x, int ldx, int xoff,
-                            const float* center, int ldc, int B, int T, int C, float eps, float* pooled, hipStream_t st) {
-    if (!ctx || !logits || !x || !pooled || B <= 0 || T <= 0 || C <= 0) VP_FAIL(ctx, VP_EINVAL, "asp: bad arguments");
-    if (B > 65535) VP_FAIL(ctx, VP_EINVAL, "asp: batch too large");
-    dim3 grid((C + 63) / 64, B);
-    if (dtype == VP_BF16) {
-        AspArgs<bf16_t> a{logits, (const bf16_t*)x, center, pooled, ldx, xoff, ldc, B, T, C, eps};
-        hipLaunchKernelGGL(asp_softmax_stats_kernel<bf16_t>, grid, dim3(256), 0, st, a);
-    } else if (dtype == VP_F32) {
-        AspArgs<float> a{logits, (const float*)x, center, pooled, ldx, xoff, ldc, B, T, C, eps};
-        static const bool plain = getenv("VPMI_ASP_STATS_PLAIN") != nullptr;          // A/B switch
-        if (T <= 160 && !plain) hipLaunchKernelGGL(asp_softmax_stats_reg_kernel<20>, grid, dim3(512), 0, st, a);
-        else if (T <= 320 && !plain) hipLaunchKernelGGL(asp_softmax_stats_reg_kernel<40>, grid, dim3(512), 0, st, a);
-        else hipLaunchKernelGGL(asp_softmax_stats_kernel<float>, grid, dim3(256), 0, st, a);
-    } else {
-        VP_FAIL(ctx, VP_EINVAL, "asp: bad dtype");
-    }
-    VP_LAUNCH_CHECK(ctx, "asp_softmax_stats");
-    return VP_OK;
-}
-
-extern "C" {
-
-int vp_asp_softmax_stats(vp_ctx* ctx, int dtype, const float* logits, const void* x, int ldx, int xoff,
-                         int B, int T, int C, float eps, float* pooled, vp_stream stream) {
-    return vp_asp_softmax_stats_ex(ctx, dtype, logits, x, ldx, xoff, nullptr, 0, B, T, C, eps, pooled, (hipStream_t)stream);
-}
-
-// f32 x, logits stored as bf16 (the training engine under enable_amp; T <= 320, else VP_EUNSUP: the caller keeps f32 logits)
-int vp_asp_softmax_stats_l16(vp_ctx* ctx, const void* logits_bf16, const void* x, int x_dtype, int ldx, int xoff, int B, int T, int C, float eps,
-                             float* pooled, vp_stream stream) {
-    if (!ctx || !logits_bf16 || !x || !pooled || B <= 0 || T <= 0 || C <= 0 || B > 65535 || (x_dtype != VP_F32 && x_dtype != VP_BF16))
-        VP_FAIL(ctx, VP_EINVAL, "asp_l16: bad arguments");
-    if (T > 320) return VP_EUNSUP;
-    AspArgs<float> a{(const float*)logits_bf16, (const float*)x, nullptr, pooled, ldx, xoff, 0, B, T, C, eps};
-    const dim3 grid((C + 63) / 64, B);
-    hipStream_t st = (hipStream_t)stream;
-    if (x_dtype == VP_BF16) {
-        if (T <= 160) hipLaunchKernelGGL((asp_softmax_stats_reg_kernel<20, bf16_t, bf16_t>), grid, dim3(512), 0, st, a);
-        else hipLaunchKernelGGL((asp_softmax_stats_reg_kernel<40, bf16_t, bf16_t>), grid, dim3(512), 0, st, a);
-    } else if (T <= 160) hipLaunchKernelGGL((asp_softmax_stats_reg_kernel<20, bf16_t>), grid, dim3(512), 0, st, a);
-    else hipLaunchKernelGGL((asp_softmax_stats_reg_kernel<40, bf16_t>), grid, dim3(512), 0, st, a);
-    VP_LAUNCH_CHECK(ctx, "asp_softmax_stats_l16");
-    return VP_OK;
 }
 
 }  // extern "C"

@@ -965,183 +965,6 @@ __global__ __launch_bounds__(256) void pack_segments_kernel(const PackArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------- per-utterance pieces (ASP)
-// out[b][c] = sum_t a[b, t, c]   (gradient of a per-utterance bias; one workgroup = 64 channels of one utterance)
-template <typename TA = float>
-__global__ __launch_bounds__(256) void utt_sums_kernel(const TA* a, int lda, int T, int C, float* out) {
-    __shared__ float sm[4][64];
-    const int lc = threadIdx.x & 63, rg = threadIdx.x >> 6;
-    const int b = blockIdx.y, c = blockIdx.x * 64 + lc;
-    float s = 0.f;
-    if (c < C)
-        for (int t = rg; t < T; t += 4) s += vp_to_f32(a[((size_t)b * T + t) * lda + c]);
-    sm[rg][lc] = s;
-    __syncthreads();
-    if (rg == 0 && c < C) out[(size_t)b * C + c] = sm[0][lc] + sm[1][lc] + sm[2][lc] + sm[3][lc];
-}
-
-// Backward of stats[b] = [mean_t x | sqrt(max(var_biased_t x, eps))] (pooling.py:97-104 with a mask of ones):
-// dx[b,t,c] = dmean / T + [var > eps] * dstd / std * (x - mean) / T
-struct TsBwdArgs { const float* x; const float* stats; const float* dstats; float* dx; int ldx, lddx, T, C4; float eps; long long total; int unbiased;
-                   const float* add; int ldadd; };     // add: other gradients of x summed in the same pass (may alias dx)
-template <typename TX = float>
-__global__ __launch_bounds__(256) void time_stats_bwd_kernel(TsBwdArgs a) {
-    const int C = a.C4 * 4;
-    const float invT = 1.f / (float)a.T;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < a.total; i += (long long)gridDim.x * 256) {
-        const long long m = i / a.C4;
-        const int c = (int)(i - m * a.C4) * 4;
-        const long long b = m / a.T;
-        float x[4], mu[4], sd[4], dm[4], ds[4], o[4];
-        vp_load4(reinterpret_cast<const TX*>(a.x) + m * a.ldx + c, x);
-        vp_load4(a.stats + b * 2 * C + c, mu); vp_load4(a.stats + b * 2 * C + C + c, sd);
-        vp_load4(a.dstats + b * 2 * C + c, dm); vp_load4(a.dstats + b * 2 * C + C + c, ds);
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            // sd = sqrt(var_unbiased + eps).  eps = 0 (CAM++'s statistics pooling, campplus.py:24-30) and a channel that is constant over an
-            // utterance's frames (a ReLU output that is zero throughout) give sd = 0: the term is 0 / 0.  Its limit -- and what autograd
-            // frameworks return for d sqrt(var) at var = 0 (torch masks it; round 5: this NaN reached Adam ~200 steps into a CAM++ run and
-            // killed the model, tools/train_dynamics_ab.py) -- is no contribution from the std
-            o[e] = a.unbiased ? dm[e] * invT + (sd[e] > 0.f ? ds[e] / sd[e] * (x[e] - mu[e]) / (float)(a.T > 1 ? a.T - 1 : 1) : 0.f)
-                              : dm[e] * invT + ((sd[e] * sd[e] > a.eps) ? ds[e] / sd[e] * (x[e] - mu[e]) * invT : 0.f);
-        if (a.add) {
-            float ad[4];
-            vp_load4(a.add + m * a.ldadd + c, ad);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] += ad[e];
-        }
-        vp_store4(a.dx + m * a.lddx + c, o);
-    }
-}
-
-// The same gradient as per-utterance coefficients: dx[b,t,c] = alpha[b,c] + beta[b,c] * x[b,t,c] with beta = [var > eps] dstd / (std T),
-// alpha = dmean / T - beta * mean -- what the BatchNorm-backward passes of the producing layer add to their d y on the fly
-// (ColSum4Args UTT == 2) instead of a pass over the (B*T, C) tensor.  ab: [2][B][C]
-__global__ __launch_bounds__(256) void time_stats_bwd_coeffs_kernel(const float* stats, const float* dstats, int B, int C, int T, float eps, float* ab) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= B * C) return;
-    const int b = i / C, c = i - b * C;
-    const float invT = 1.f / (float)T;
-    const float mu = stats[(size_t)b * 2 * C + c], sd = stats[(size_t)b * 2 * C + C + c];
-    const float dm = dstats[(size_t)b * 2 * C + c], ds = dstats[(size_t)b * 2 * C + C + c];
-    const float be = (sd * sd > eps) ? ds / sd * invT : 0.f;
-    ab[i] = __fmaf_rn(-be, mu, dm * invT);
-    ab[(size_t)B * C + i] = be;
-}
-
-// Backward of attentive statistics (pooling.py:114-123): alpha = softmax_t(e), mu = sum alpha x, sd = sqrt(max(sum alpha (x-mu)^2, eps)).
-//   dv = [sd^2 > eps] dsd / (2 sd);  dalpha_t = dmu x_t + dv (x_t - mu)^2;  S = sum_t alpha_t dalpha_t
-//   de_t = alpha_t (dalpha_t - S);   dx_t = alpha_t (dmu + 2 dv (x_t - mu))
-// One workgroup = 64 channels of one utterance, three passes over its frames (max; normaliser and S; outputs).
-struct AsBwdArgs { const float* e; const float* x; const float* pooled; const float* dpooled; float* de; float* dx; int ldx, lddx, T, C; float eps; };
-// TE = bf16_t: d e leaves as bf16 (a.de reinterpreted) -- the operand the logits conv's two backward GEMMs would round it to anyway
-template <typename TE>
-__global__ __launch_bounds__(256) void attn_stats_bwd_kernel(AsBwdArgs a) {
-    __shared__ float sm[2][4][64];
-    const int lc = threadIdx.x & 63, rg = threadIdx.x >> 6;
-    const int b = blockIdx.y, c = blockIdx.x * 64 + lc;
-    const bool ok = c < a.C;
-    const int cc = ok ? c : 0;
-    const float* eb = a.e + (size_t)b * a.T * a.C + cc;
-    const float* xb = a.x + (size_t)b * a.T * a.ldx + cc;
-    const float mu = a.pooled[(size_t)b * 2 * a.C + cc], sd = a.pooled[(size_t)b * 2 * a.C + a.C + cc];
-    const float dmu = a.dpooled[(size_t)b * 2 * a.C + cc], dsd = a.dpooled[(size_t)b * 2 * a.C + a.C + cc];
-    const float dv = (sd * sd > a.eps) ? dsd / (2.f * sd) : 0.f;
-    float mx = -INFINITY;
-    for (int t = rg; t < a.T; t += 4) mx = fmaxf(mx, eb[(size_t)t * a.C]);
-    sm[0][rg][lc] = mx;
-    __syncthreads();
-    mx = fmaxf(fmaxf(sm[0][0][lc], sm[0][1][lc]), fmaxf(sm[0][2][lc], sm[0][3][lc]));
-    __syncthreads();
-    float z = 0.f, u = 0.f;
-    for (int t = rg; t < a.T; t += 4) {
-        const float p = expf(eb[(size_t)t * a.C] - mx);
-        const float xv = xb[(size_t)t * a.ldx], d = xv - mu;
-        z += p; u += p * (dmu * xv + dv * d * d);
-    }
-    sm[0][rg][lc] = z; sm[1][rg][lc] = u;
-    __syncthreads();
-    z = sm[0][0][lc] + sm[0][1][lc] + sm[0][2][lc] + sm[0][3][lc];
-    u = sm[1][0][lc] + sm[1][1][lc] + sm[1][2][lc] + sm[1][3][lc];
-    const float S = u / z;
-    if (!ok) return;
-    for (int t = rg; t < a.T; t += 4) {
-        const float al = expf(eb[(size_t)t * a.C] - mx) / z;
-        const float xv = xb[(size_t)t * a.ldx], d = xv - mu;
-        reinterpret_cast<TE*>(a.de)[((size_t)b * a.T + t) * a.C + c] = (TE)(al * (dmu * xv + dv * d * d - S));
-        a.dx[((size_t)b * a.T + t) * a.lddx + c] = al * (dmu + 2.f * dv * d);
-    }
-}
-
-// The same with the thread's share of e and x kept in REGISTERS between the passes: one workgroup = 64 channels of one utterance,
-// 512 threads = 8 frame groups, NT = ceil(T / 8) <= 40 values of each per thread (T <= 320).  The plain kernel above re-reads both
-// slices from HBM in its second and third pass (PMC: 2.35 GB read per launch at B = 256 for 0.94 GB of inputs -- 552 us, the largest
-// kernel of the backward pass bar the weight gradients); here every input byte is read once.  (An LDS-resident variant -- 76 KB per
-// workgroup, two per CU -- measured SLOWER than the plain kernel: 8 waves per CU cannot keep enough loads in flight.)
-template <typename TE, int NT, typename TL = float, typename TX = float>
-__global__ __launch_bounds__(512) void attn_stats_bwd_reg_kernel(AsBwdArgs a) {
-    __shared__ float sm[2][8][64];
-    const int lc = threadIdx.x & 63, rg = threadIdx.x >> 6;
-    const int b = blockIdx.y, c = blockIdx.x * 64 + lc;
-    const bool ok = c < a.C;
-    const int cc = ok ? c : 0;
-    const TL* eb = reinterpret_cast<const TL*>(a.e) + (size_t)b * a.T * a.C + cc;        // TL = bf16: the logits as the forward stored them
-    const TX* xb = reinterpret_cast<const TX*>(a.x) + (size_t)b * a.T * a.ldx + cc;     // TX = bf16: x as its producer stored it
-    const float mu = a.pooled[(size_t)b * 2 * a.C + cc], sd = a.pooled[(size_t)b * 2 * a.C + a.C + cc];
-    const float dmu = a.dpooled[(size_t)b * 2 * a.C + cc], dsd = a.dpooled[(size_t)b * 2 * a.C + a.C + cc];
-    const float dv = (sd * sd > a.eps) ? dsd / (2.f * sd) : 0.f;
-    float ev[NT], xv[NT];
-#pragma unroll
-    for (int i = 0; i < NT; ++i) {                  // (unconditional loads on a clamped frame; the uses below are predicated)
-        const int t = min(rg + 8 * i, a.T - 1);
-        ev[i] = vp_to_f32(eb[(size_t)t * a.C]);
-        xv[i] = vp_to_f32(xb[(size_t)t * a.ldx]);
-    }
-    float mx = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < NT; ++i) if (rg + 8 * i < a.T) mx = fmaxf(mx, ev[i]);
-    sm[0][rg][lc] = mx;
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < 8; ++q) mx = fmaxf(mx, sm[0][q][lc]);
-    __syncthreads();
-    float z = 0.f, u = 0.f;
-#pragma unroll
-    for (int i = 0; i < NT; ++i) {
-        const float p = rg + 8 * i < a.T ? expf(ev[i] - mx) : 0.f;
-        const float d = xv[i] - mu;
-        ev[i] = p;                                  // exp(e - max): the third pass needs nothing else of e
-        z += p; u += p * (dmu * xv[i] + dv * d * d);
-    }
-    sm[0][rg][lc] = z; sm[1][rg][lc] = u;
-    __syncthreads();
-    z = 0.f; u = 0.f;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) { z += sm[0][q][lc]; u += sm[1][q][lc]; }
-    const float S = u / z;
-    if (!ok) return;
-#pragma unroll
-    for (int i = 0; i < NT; ++i) {
-        const int t = rg + 8 * i;
-        if (t < a.T) {
-            const float al = ev[i] / z;
-            const float d = xv[i] - mu;
-            reinterpret_cast<TE*>(a.de)[((size_t)b * a.T + t) * a.C + c] = (TE)(al * (dmu * xv[i] + dv * d * d - S));
-            a.dx[((size_t)b * a.T + t) * a.lddx + c] = al * (dmu + 2.f * dv * d);
-        }
-    }
-}
-
-template <typename TE>
-static int launch_attn_stats_bwd(vp_ctx* ctx, const AsBwdArgs& a, int B, hipStream_t st) {
-    (void)ctx;
-    const dim3 grid((a.C + 63) / 64, B);
-    static const bool plain = getenv("VPMI_ASB_PLAIN") != nullptr;      // A/B switch, read once per process
-    if (a.T <= 160 && !plain) hipLaunchKernelGGL((attn_stats_bwd_reg_kernel<TE, 20>), grid, dim3(512), 0, st, a);
-    else if (a.T <= 320 && !plain) hipLaunchKernelGGL((attn_stats_bwd_reg_kernel<TE, 40>), grid, dim3(512), 0, st, a);
-    else hipLaunchKernelGGL(attn_stats_bwd_kernel<TE>, grid, dim3(256), 0, st, a);
-    return VP_OK;
-}
-
 // Adjoint of reflect padding: dxp (B, T + 2p, C) is the gradient w.r.t. the reflect-padded input (from the zero-padded
 // "full" data-gradient conv); frames 1..p and T-1-p..T-2 also receive their mirror images' gradients.
 struct FoldArgs { const float* dxp; float* dx; int T, p, C4; long long total;
@@ -1904,14 +1727,6 @@ int vp_bn_relu_bwd_dbias_b16(vp_ctx* ctx, const float* dy, int lddy, const void*
     return bn_bwd_dbias_impl(ctx, dy, lddy, z, ldz, mean, invstd, gamma, sums, M, C, relu_mask, dz, lddz, true, dbias, ws, ws_bytes, stream, true);
 }
 
-// alpha / beta of the context-statistics gradient (time_stats_bwd_coeffs_kernel): ab [2][B][C]
-int vp_time_stats_bwd_coeffs(vp_ctx* ctx, const float* stats, const float* dstats, int B, int T, int C, float eps, float* ab, vp_stream stream) {
-    if (!ctx || !stats || !dstats || !ab || B <= 0 || T <= 0 || C <= 0) VP_FAIL(ctx, VP_EINVAL, "time_stats_bwd_coeffs: bad arguments");
-    hipLaunchKernelGGL(time_stats_bwd_coeffs_kernel, dim3((B * C + 255) / 256), dim3(256), 0, (hipStream_t)stream, stats, dstats, B, C, T, eps, ab);
-    VP_LAUNCH_CHECK(ctx, "time_stats_bwd_coeffs");
-    return VP_OK;
-}
-
 // The two BatchNorm-backward passes of a TDNNBlock whose output y = BN(z) is consumed by a pooling layer's context statistics: d y =
 // dy + alpha[b] + beta[b] * bf16(z * bn_scale + bn_shift) (vp_time_stats_bwd_coeffs), y re-formed from the bf16 z the passes read anyway --
 // vp_time_stats_bwd_add_x16's pass over the (B*T, C) tensors never runs.  sums: [2][C]
@@ -2046,94 +1861,6 @@ int vp_pack_segments_f32(vp_ctx* ctx, const void* const* srcs, const long long* 
         hipLaunchKernelGGL(pack_segments_kernel, dim3((unsigned)bx, cnt), dim3(256), 0, (hipStream_t)stream, a);
         VP_LAUNCH_CHECK(ctx, "pack_segments");
     }
-    return VP_OK;
-}
-
-int vp_utt_sums_b16(vp_ctx* ctx, const void* a_bf16, int lda, int B, int T, int C, float* out, vp_stream stream) {
-    if (!ctx || !a_bf16 || !out || B <= 0 || T <= 0 || C <= 0 || B > 65535) VP_FAIL(ctx, VP_EINVAL, "utt_sums_b16: bad arguments");
-    hipLaunchKernelGGL(utt_sums_kernel<bf16_t>, dim3((C + 63) / 64, B), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)a_bf16, lda, T, C, out);
-    VP_LAUNCH_CHECK(ctx, "utt_sums_b16");
-    return VP_OK;
-}
-
-int vp_utt_sums_f32(vp_ctx* ctx, const float* a, int lda, int B, int T, int C, float* out, vp_stream stream) {
-    if (!ctx || !a || !out || B <= 0 || T <= 0 || C <= 0 || B > 65535) VP_FAIL(ctx, VP_EINVAL, "utt_sums: bad arguments");
-    hipLaunchKernelGGL(utt_sums_kernel<float>, dim3((C + 63) / 64, B), dim3(256), 0, (hipStream_t)stream, a, lda, T, C, out);
-    VP_LAUNCH_CHECK(ctx, "utt_sums");
-    return VP_OK;
-}
-
-int vp_time_stats_f32(vp_ctx* ctx, const float* x, int ldx, int B, int T, int C, float eps, int unbiased, float* stats, vp_stream stream) {
-    if (!ctx || !x || !stats || B <= 0 || T <= 0 || C <= 0) VP_FAIL(ctx, VP_EINVAL, "time_stats: bad arguments");
-    return vp_time_moments(ctx, VP_F32, x, ldx, B, T, C, eps, unbiased, stats, (hipStream_t)stream);
-}
-
-int vp_time_stats_bwd_f32(vp_ctx* ctx, const float* x, int ldx, const float* stats, const float* dstats, int B, int T, int C, float eps,
-                          int unbiased, float* dx, int lddx, vp_stream stream) {
-    if (!ctx || !x || !stats || !dstats || !dx || B <= 0 || T <= 0 || C <= 0 || (C | ldx | lddx) & 3) VP_FAIL(ctx, VP_EINVAL, "time_stats_bwd: bad arguments");
-    TsBwdArgs a{x, stats, dstats, dx, ldx, lddx, T, C / 4, eps, (long long)B * T * (C / 4), unbiased, nullptr, 0};
-    hipLaunchKernelGGL(time_stats_bwd_kernel<float>, dim3(grid1d(a.total)), dim3(256), 0, (hipStream_t)stream, a);
-    VP_LAUNCH_CHECK(ctx, "time_stats_bwd");
-    return VP_OK;
-}
-
-// dx = add + (the gradient through the statistics): the other consumers' gradients of x folded into this pass (add may be dx)
-int vp_time_stats_bwd_add_f32(vp_ctx* ctx, const float* x, int ldx, const float* stats, const float* dstats, int B, int T, int C, float eps,
-                              int unbiased, const float* add, int ldadd, float* dx, int lddx, vp_stream stream) {
-    if (!ctx || !x || !stats || !dstats || !dx || !add || B <= 0 || T <= 0 || C <= 0 || (C | ldx | lddx | ldadd) & 3)
-        VP_FAIL(ctx, VP_EINVAL, "time_stats_bwd_add: bad arguments");
-    TsBwdArgs a{x, stats, dstats, dx, ldx, lddx, T, C / 4, eps, (long long)B * T * (C / 4), unbiased, add, ldadd};
-    hipLaunchKernelGGL(time_stats_bwd_kernel<float>, dim3(grid1d(a.total)), dim3(256), 0, (hipStream_t)stream, a);
-    VP_LAUNCH_CHECK(ctx, "time_stats_bwd_add");
-    return VP_OK;
-}
-
-// the same with x stored as bf16 (ldx in elements)
-int vp_time_stats_bwd_add_x16(vp_ctx* ctx, const void* x_bf16, int ldx, const float* stats, const float* dstats, int B, int T, int C, float eps,
-                              int unbiased, const float* add, int ldadd, float* dx, int lddx, vp_stream stream) {
-    if (!ctx || !x_bf16 || !stats || !dstats || !dx || !add || B <= 0 || T <= 0 || C <= 0 || (C | ldx | lddx | ldadd) & 3)
-        VP_FAIL(ctx, VP_EINVAL, "time_stats_bwd_add_x16: bad arguments");
-    TsBwdArgs a{(const float*)x_bf16, stats, dstats, dx, ldx, lddx, T, C / 4, eps, (long long)B * T * (C / 4), unbiased, add, ldadd};
-    hipLaunchKernelGGL(time_stats_bwd_kernel<bf16_t>, dim3(grid1d(a.total)), dim3(256), 0, (hipStream_t)stream, a);
-    VP_LAUNCH_CHECK(ctx, "time_stats_bwd_add_x16");
-    return VP_OK;
-}
-
-int vp_attn_stats_bwd_f32(vp_ctx* ctx, const float* e, const float* x, int ldx, const float* pooled, const float* dpooled, int B, int T,
-                          int C, float eps, float* de, float* dx, int lddx, vp_stream stream) {
-    if (!ctx || !e || !x || !pooled || !dpooled || !de || !dx || B <= 0 || T <= 0 || C <= 0 || B > 65535) VP_FAIL(ctx, VP_EINVAL, "attn_stats_bwd: bad arguments");
-    AsBwdArgs a{e, x, pooled, dpooled, de, dx, ldx, lddx, T, C, eps};
-    { const int rc = launch_attn_stats_bwd<float>(ctx, a, B, (hipStream_t)stream); if (rc) return rc; }
-    VP_LAUNCH_CHECK(ctx, "attn_stats_bwd");
-    return VP_OK;
-}
-
-// d e written as bf16 ((B*T, C) dense): mixed precision, the logits conv's backward GEMMs then read bf16 operands
-// d e bf16 AND e stored as bf16 (vp_asp_softmax_stats_l16's logits); T <= 320, else VP_EUNSUP
-int vp_attn_stats_bwd_e16(vp_ctx* ctx, const void* e_bf16, const void* x, int x_dtype, int ldx, const float* pooled, const float* dpooled, int B,
-                          int T, int C, float eps, void* de_bf16, float* dx, int lddx, vp_stream stream) {
-    if (!ctx || !e_bf16 || !x || !pooled || !dpooled || !de_bf16 || !dx || B <= 0 || T <= 0 || C <= 0 || B > 65535 ||
-        (x_dtype != VP_F32 && x_dtype != VP_BF16))
-        VP_FAIL(ctx, VP_EINVAL, "attn_stats_bwd_e16: bad arguments");
-    if (T > 320) return VP_EUNSUP;
-    AsBwdArgs a{(const float*)e_bf16, (const float*)x, pooled, dpooled, (float*)de_bf16, dx, ldx, lddx, T, C, eps};
-    const dim3 grid((C + 63) / 64, B);
-    hipStream_t st = (hipStream_t)stream;
-    if (x_dtype == VP_BF16) {
-        if (T <= 160) hipLaunchKernelGGL((attn_stats_bwd_reg_kernel<bf16_t, 20, bf16_t, bf16_t>), grid, dim3(512), 0, st, a);
-        else hipLaunchKernelGGL((attn_stats_bwd_reg_kernel<bf16_t, 40, bf16_t, bf16_t>), grid, dim3(512), 0, st, a);
-    } else if (T <= 160) hipLaunchKernelGGL((attn_stats_bwd_reg_kernel<bf16_t, 20, bf16_t>), grid, dim3(512), 0, st, a);
-    else hipLaunchKernelGGL((attn_stats_bwd_reg_kernel<bf16_t, 40, bf16_t>), grid, dim3(512), 0, st, a);
-    VP_LAUNCH_CHECK(ctx, "attn_stats_bwd_e16");
-    return VP_OK;
-}
-
-int vp_attn_stats_bwd_de16(vp_ctx* ctx, const float* e, const float* x, int ldx, const float* pooled, const float* dpooled, int B, int T,
-                           int C, float eps, void* de, float* dx, int lddx, vp_stream stream) {
-    if (!ctx || !e || !x || !pooled || !dpooled || !de || !dx || B <= 0 || T <= 0 || C <= 0 || B > 65535) VP_FAIL(ctx, VP_EINVAL, "attn_stats_bwd: bad arguments");
-    AsBwdArgs a{e, x, pooled, dpooled, (float*)de, dx, ldx, lddx, T, C, eps};
-    { const int rc = launch_attn_stats_bwd<bf16_t>(ctx, a, B, (hipStream_t)stream); if (rc) return rc; }
-    VP_LAUNCH_CHECK(ctx, "attn_stats_bwd_de16");
     return VP_OK;
 }
 

@@ -3,7 +3,7 @@
 AttentiveStatisticsPooling (pooling.py:69-125) is the one on the hot path; it runs inside the
 model's fused forward (csrc/ecapa.hip run_asp): the global-context mean/std come from sums fused
 into the producing conv, their 2C columns of the attention TDNN collapse to a per-utterance bias,
-and softmax + weighted mean/std run in one pass (csrc/small_ops.hip).
+and softmax + weighted mean/std run in one pass (csrc/pooling_stats.hip).
 """
 from torch import nn
 
