@@ -1029,6 +1029,23 @@ size_t vp_affinity_prune_workspace_bytes(int N, int D);
 int vp_affinity_prune_f32(vp_ctx* ctx, const float* emb, int N, int D, int n_elems, float* P, void* ws, size_t ws_bytes,
                           vp_stream stream);
 int vp_laplacian_f32(vp_ctx* ctx, const float* P, int N, float* L, vp_stream stream);
+/* vp_eigs_init_f32 / vp_eigs_iterate_f32 -- the k smallest eigenpairs of L as vp_laplacian_f32 writes it (symmetric, positive
+ *   semi-definite), replacing scipy.linalg.eigh in SpectralCluster.get_spec_embs (:228-236), which reads 16 eigenvalues and at most 15
+ *   vectors of the full decomposition (csrc/diarize_eigs.hip, docs/diarize_eigs.md).  Chebyshev-filtered subspace iteration on a block
+ *   of 32 vectors; products on the exact-f32 matrix cores, float64 only in the Gram sums, the 32 x 32 projected problem and the rotation.
+ *   init: sigma = 2 max L_ii (Gershgorin: the spectrum lies in [0, sigma]), a start block hashed from (row, column), one Rayleigh-Ritz
+ *   step (which orthonormalises it).  iterate: `steps` filter steps (1 <= steps <= 64) that damp [largest Ritz value of the block,
+ *   sigma], then one Rayleigh-Ritz step.  Both write evals[k] ascending, evecs (N, k) row-major with vector j in column j (orthonormal),
+ *   resid[j] = |L v_j - lambda_j v_j|_2 and bounds = (sigma, the block's largest Ritz value); the caller reads them back once per round
+ *   and decides whether to go on.  The state between calls is the workspace: the same ws, L, N and k from init through every iterate.
+ *   64 <= N <= 16384 (else VP_EUNSUP), 1 <= k <= 24 (else VP_EINVAL, checked first), workspace too small: VP_EWORKSPACE; nothing is
+ *   launched then.  L = 0: zero eigenvalues, the first k unit vectors, zero residuals.  No float atomics, no grid barrier, no host
+ *   synchronisation: two runs give the same bits. */
+size_t vp_eigs_workspace_bytes(int N, int k);
+int vp_eigs_init_f32(vp_ctx* ctx, const float* L, int N, int k, void* ws, size_t ws_bytes, float* evals, float* evecs, float* resid,
+                     float* bounds, vp_stream stream);
+int vp_eigs_iterate_f32(vp_ctx* ctx, const float* L, int N, int k, int steps, void* ws, size_t ws_bytes, float* evals, float* evecs,
+                        float* resid, float* bounds, vp_stream stream);
 
 #ifdef __cplusplus
 }

@@ -88,6 +88,25 @@ def get_train_x3():
     return _TRAIN_X3 and not _TRAIN_AMP
 
 
+_SPECTRAL_SOLVER = 'host'
+
+
+def set_spectral_solver(name):
+    """Where the diarization's spectral step finds the Laplacian's smallest eigenpairs (infer_utils/speaker_diarization.py):
+    'host'  scipy.linalg.eigh of the whole matrix on the CPU, as the reference does -- the default;
+    'gpu'   Chebyshev-filtered subspace iteration in HIP on the Laplacian where it was built (csrc/diarize_eigs.hip), for
+            64 <= N <= 16384 windows and at most 24 wanted eigenvalues; outside that range, or when the iteration does not converge
+            within its caps (a RuntimeWarning says so), the host path runs."""
+    global _SPECTRAL_SOLVER
+    if name not in ('host', 'gpu'):
+        raise ValueError(f'unsupported spectral solver {name}')
+    _SPECTRAL_SOLVER = name
+
+
+def get_spectral_solver():
+    return _SPECTRAL_SOLVER
+
+
 _FUSED_GRID_KERNELS = True
 
 

@@ -4,11 +4,21 @@ What runs in HIP (csrc/diarize.hip): the batch of fixed-length windows (``chunk_
 decibel normalisation of predict.py:213-215), the pruned cosine affinity (``affinity_prune``: get_sim_mat + p_pruning, :253-273) and the
 Laplacian (``laplacian``: :246, :276-282).  There is no CPU path: these raise ``VpmiError`` without a GPU.
 Host arithmetic kept in Python as in the reference: the chunk table, label bookkeeping, merging and smoothing, the eigen-gap rule;
-``scipy.linalg.eigh`` and ``sklearn.cluster.k_means`` run on the host exactly as they do there.
+``sklearn.cluster.k_means`` runs on the host exactly as it does there.
+
+The Laplacian's eigenpairs have two solvers (``ppvector.set_spectral_solver``).  'host', the default, is the reference's
+``scipy.linalg.eigh`` of the whole matrix.  'gpu' is ``smallest_eigenpairs``: Chebyshev-filtered subspace iteration in HIP
+(csrc/diarize_eigs.hip, docs/diarize_eigs.md) for the max_num_spks + 1 eigenvalues the gap rule reads (or the oracle_num vectors asked
+for) on the Laplacian where it was built, without copying it to the host; it is taken for 64 <= N <= 16384 windows and at most 24 wanted
+eigenvalues, and hands over to the host path (with a RuntimeWarning) when it does not converge within its caps.
 
 Voice-activity detection is NOT built: the reference uses yeaudio's model-based ``AudioSegment.vad`` (:37).  ``segments`` takes the
 speech regions from the caller instead.
 """
+import math
+import warnings
+from types import SimpleNamespace
+
 import numpy as np
 import torch
 
@@ -60,6 +70,64 @@ def laplacian(pruned):
     out = torch.empty_like(p)
     N.check(lib.vp_laplacian_f32(ctx, N.ptr(p), p.shape[0], N.ptr(out), N.stream_ptr()), ctx)
     return out
+
+
+# Defaults of smallest_eigenpairs (docs/diarize_eigs.md has the measurements behind them).  A round is one filter plus one Rayleigh-Ritz
+# step; the filter's degree is chosen per round so that it amplifies the eigenvalue 0 over the block's largest Ritz value by at most
+# EIGS_MAX_AMPLIFICATION: beyond that the filtered block is too ill-conditioned for one Cholesky orthonormalisation of f32 vectors.
+EIGS_TOL = 1e-6                    # stop when every wanted |L v - lambda v| <= EIGS_TOL * sigma
+EIGS_MAX_ROUNDS = 40
+EIGS_MAX_DEGREE = 40
+EIGS_MAX_AMPLIFICATION = 1e4
+EIGS_MIN_N, EIGS_MAX_N, EIGS_MAX_K = 64, 16384, 24
+_eigs_ws = N.Workspace()
+
+
+def _filter_degree(sigma, upper):
+    """Degree m with T_m((sigma + a) / (sigma - a)) <= EIGS_MAX_AMPLIFICATION, a = upper: T_m(t) = cosh(m acosh t) outside [-1, 1]."""
+    if not (sigma > upper > 0.0):
+        return 2
+    t0 = math.acosh((sigma + upper) / (sigma - upper))
+    if t0 <= 0.0:
+        return EIGS_MAX_DEGREE
+    return int(max(2, min(EIGS_MAX_DEGREE, math.floor(math.acosh(EIGS_MAX_AMPLIFICATION) / t0))))
+
+
+def smallest_eigenpairs(L, k, tol=None, max_rounds=None):
+    """The k smallest eigenpairs of the symmetric positive semi-definite (N, N) float32 GPU tensor L (``laplacian``'s output):
+    -> (eigenvalues (k,) float64 ndarray ascending, eigenvectors (N, k) float32 ndarray, orthonormal, info).
+    vp_eigs_init_f32 once, then rounds of vp_eigs_iterate_f32; after each the k residuals |L v - lambda v|_2 (with the eigenvalues and the
+    two interval ends, one small copy) are read back and the loop stops once all are <= tol * sigma, sigma = 2 max L_ii, or after
+    max_rounds rounds.  ``info``: rounds, products (block products L X spent), residuals (k,), sigma, converged."""
+    if not isinstance(L, torch.Tensor) or not L.is_cuda:
+        raise N.VpmiError('smallest_eigenpairs needs a GPU tensor: the engine has no CPU fallback')
+    if L.dim() != 2 or L.shape[0] != L.shape[1]:
+        raise ValueError('smallest_eigenpairs: L must be square')
+    L = L.contiguous().float()
+    n, k = L.shape[0], int(k)
+    tol = EIGS_TOL if tol is None else float(tol)
+    max_rounds = EIGS_MAX_ROUNDS if max_rounds is None else int(max_rounds)
+    lib, ctx = N.lib(), N.ctx(L.device)
+    nbytes = lib.vp_eigs_workspace_bytes(n, k)
+    ws = _eigs_ws.get(nbytes, L.device)
+    out = torch.empty(2 * k + 2, dtype=torch.float32, device=L.device)          # eigenvalues | residuals | sigma, largest Ritz value
+    vecs = torch.empty((n, max(k, 1)), dtype=torch.float32, device=L.device)
+    esz = out.element_size()
+    args = (N.ptr(ws), nbytes, N.ptr(out), N.ptr(vecs), N.ptr(out) + k * esz, N.ptr(out) + 2 * k * esz, N.stream_ptr())
+    N.check(lib.vp_eigs_init_f32(ctx, N.ptr(L), n, k, *args), ctx)
+    rounds, products = 0, 1
+    while True:
+        host = out.cpu().numpy().astype(np.float64)
+        sigma, upper = host[2 * k], host[2 * k + 1]
+        converged = bool(np.all(host[k:2 * k] <= tol * sigma))                  # a NaN residual is not converged
+        if converged or rounds >= max_rounds:
+            break
+        steps = _filter_degree(sigma, upper)
+        N.check(lib.vp_eigs_iterate_f32(ctx, N.ptr(L), n, k, steps, *args), ctx)
+        rounds += 1
+        products += steps + 1
+    info = SimpleNamespace(rounds=rounds, products=products, residuals=host[k:2 * k].copy(), sigma=float(sigma), converged=converged)
+    return host[:k].copy(), vecs.cpu().numpy(), info
 
 
 # ------------------------------------------------------------------------------------------------ the reference's classes
@@ -221,13 +289,31 @@ class SpectralCluster:
         return laplacian(affinity_prune(x, self.n_elems(x.shape[0])))
 
     def __call__(self, X, oracle_num=None):
-        L = self.laplacian(X).cpu().numpy()
-        emb, num_of_spk = self.get_spec_embs(L, oracle_num)
+        emb, num_of_spk = self.get_spec_embs(self.laplacian(X), oracle_num)
         return self.cluster_embs(emb, num_of_spk)
 
+    def _gpu_eigenpairs(self, L, k_oracle):
+        """The wanted eigenpairs from the GPU solver, or None where the host path has to run: the switch is on 'host', L is not on
+        the GPU, the size or the count is outside the solver's range, or it did not converge (the only case that warns)."""
+        import ppvector
+        if ppvector.get_spectral_solver() != 'gpu' or not isinstance(L, torch.Tensor) or not L.is_cuda:
+            return None
+        wanted = self.max_num_spks + 1 if k_oracle is None else int(k_oracle)
+        if not (EIGS_MIN_N <= L.shape[0] <= EIGS_MAX_N and 1 <= wanted <= EIGS_MAX_K):
+            return None
+        lambdas, eig_vecs, info = smallest_eigenpairs(L, wanted)
+        if not info.converged:
+            warnings.warn(f'spectral solver: worst residual {np.max(info.residuals) / max(info.sigma, 1e-300):.3g} sigma after '
+                          f'{info.rounds} rounds (tolerance {EIGS_TOL:g}); running scipy.linalg.eigh on the host', RuntimeWarning)
+            return None
+        return lambdas, eig_vecs
+
     def get_spec_embs(self, L, k_oracle=None):
-        import scipy.linalg
-        lambdas, eig_vecs = scipy.linalg.eigh(L)
+        pairs = self._gpu_eigenpairs(L, k_oracle)
+        if pairs is None:
+            import scipy.linalg
+            pairs = scipy.linalg.eigh(L.cpu().numpy() if isinstance(L, torch.Tensor) else L)
+        lambdas, eig_vecs = pairs
         if k_oracle is not None:
             num_of_spk = k_oracle
         else:
