@@ -214,6 +214,7 @@ def test_tdnn_training_step_vs_oracle_autograd(N):
     with torch.no_grad():
         head.weight.copy_(Wh.cuda())
     emb = m(x.cuda())
+    print(f'[tdnn train] embeddings rel-L2 {rel(emb, emb_ref.detach()):.2e} (bound 2e-05)')
     assert rel(emb, emb_ref.detach()) < 2e-5
     loss = HeadLoss.apply(emb, head.weight, labels.cuda(), 0.2, 32.0, 0.0, False)[0]
     assert abs(loss.item() - loss_ref.item()) < 2e-4 * abs(loss_ref.item())
@@ -225,7 +226,7 @@ def test_tdnn_training_step_vs_oracle_autograd(N):
             continue
         r = rel(v.grad, pr[k].grad)
         worst = max(worst, r)
-        assert r < 5e-4, (k, r)
+        assert r < 1e-4, (k, r)                     # (2.0e-5 measured since bn5's input is centred; 8.1e-5 before)
     assert rel(head.weight.grad, Wr.grad) < 5e-4
     print(f'[tdnn train] loss {loss.item():.5f} (oracle {loss_ref.item():.5f}); worst parameter-gradient rel-L2 {worst:.2e}')
     mean1, var1 = stats['bn1.']
@@ -258,14 +259,19 @@ def test_ecapa_training_step_vs_oracle_autograd(N, mode):
 def _ecapa_step_vs_oracle(mode):
     from ppvector.models.ecapa_tdnn import EcapaTdnn
     from ppvector.train.functions import HeadLoss
-    # batch statistics over 4 x 50 frames amplify rounding ~1e4 x (the exact-f32 step lands 7e-4 from float64 there); the split-precision
-    # step (2^-17 per product against f32's 2^-24) is therefore checked on a better-conditioned batch, 12 x 120 frames
+    # At 4 x 50 frames the exact-f32 step's worst parameter gradient (mfa.conv.conv.bias, a sum of cancelling terms) lies 7.2e-4 from float64,
+    # the whole gradient 2.4e-4: that is this graph at 200 rows per batch statistic, and it did not move when asp_bn's statistics stopped
+    # losing (mean / std)^2 ~ 4e3 roundings (BNRows centres its input, docs/bn_train.md) -- the embeddings did, 1.2e-5 -> 3.5e-6, and the
+    # loss, 1.0e-6 -> 1.8e-7.  The split-precision step (2^-17 per product against f32's 2^-24) is checked on a better-conditioned batch,
+    # 12 x 120 frames
     B, T, Cc = (4, 50, 30) if mode == 'f32' else (12, 120, 30)
     # At random init this graph turns a forward error e into a gradient error of ~150 e whatever the arithmetic (measured at 12 x 120:
     # torch's own float32 autograd of the oracle graph: embeddings 1.7e-6 / whole gradient 7.9e-4 from float64; the exact-f32 engine 5.2e-6 /
     # 7.0e-4; split precision 2.6e-5 / 5.9e-3; enable_amp 1.3e-2 / 1.5e-1).  So the split-precision gradient is held RELATIVE to float32
     # autograd's own deviation (12 x), per parameter to 5e-2 (bias gradients are sums of cancelling terms), and the embeddings to 1e-4.
-    e_tol, l_tol, g_tol, w_tol = (5e-5, 2e-4, 2e-3, 1e-3) if mode == 'f32' else (1e-4, 5e-4, 5e-2, 5e-3)
+    # f32: embeddings, loss and whole gradient 4 x what the step measures (3.5e-6, 1.8e-7, 2.4e-4); the worst parameter stays at 2e-3 (4 x
+    # its 7.2e-4 would loosen it)
+    e_tol, l_tol, g_tol, w_tol = (1.4e-5, 7.5e-7, 2e-3, 1e-3) if mode == 'f32' else (1e-4, 5e-4, 5e-2, 5e-3)
     p = om.ecapa_params(80, seed=21)
     g = torch.Generator().manual_seed(6)
     x = torch.randn(B, T, 80, generator=g) * 2
@@ -281,8 +287,10 @@ def _ecapa_step_vs_oracle(mode):
     m = m.cuda().train()
     Wd = Wh.cuda().requires_grad_()
     emb = m(x.cuda())
-    assert rel(emb, emb_ref.detach()) < e_tol
     loss = HeadLoss.apply(emb, Wd, labels.cuda(), 0.2, 32.0, 0.0, False)[0]
+    print(f'[ecapa train {mode}] embeddings rel-L2 {rel(emb, emb_ref.detach()):.2e} (bound {e_tol:.1e}); loss off by '
+          f'{abs(loss.item() - loss_ref.item()) / abs(loss_ref.item()):.2e} (bound {l_tol:.0e})')
+    assert rel(emb, emb_ref.detach()) < e_tol
     assert abs(loss.item() - loss_ref.item()) < l_tol * abs(loss_ref.item())
     loss.backward()
     worst, wk, num, den = 0.0, '', 0.0, 0.0
@@ -298,7 +306,7 @@ def _ecapa_step_vs_oracle(mode):
         assert r < g_tol, (k, r)
     assert rel(Wd.grad, Wr.grad) < w_tol
     whole = (num / den) ** 0.5
-    whole_tol = 2e-3
+    whole_tol = 1e-3
     if mode != 'f32':                                     # the yardstick: float32 autograd of the same oracle graph against its float64 run
         p32 = {k: v.clone().float().requires_grad_(not k.endswith(('_mean', '_variance'))) for k, v in p.items()}
         W32 = Wh.clone().float().requires_grad_()

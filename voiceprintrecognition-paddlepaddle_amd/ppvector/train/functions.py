@@ -93,6 +93,45 @@ def col_sums(a, b=None, bmean=None, bscale=None):
     return out
 
 
+def _affine_rows(z, ldz, rows, Cc, scale, shift, out, relu=0):
+    """out (rows, Cc, contiguous) = z * scale + shift [-> ReLU]; z read with row pitch ldz"""
+    lib, hctx = N.lib(), N.ctx(out.device)
+    _chk(lib.vp_affine_rows_f32(hctx, z.data_ptr(), ldz, scale.data_ptr(), shift.data_ptr(), rows, Cc, out.data_ptr(), Cc, relu, N.stream_ptr()), hctx)
+    return out
+
+
+def bn_centred_stats(x, ldx, M, Cc, gamma, beta, run_mean, run_var, momentum, eps):
+    """Batch statistics of the (M, Cc) f32 tensor at x (row pitch ldx; Cc, ldx multiples of 4), taken of d = x - c, c the mean of the
+    first (up to eight) rows -> d (M, Cc), negc = -c, mean (of d), invstd, scale, shift (= beta - mean scale: the apply pass runs on d);
+    the running statistics are updated as those of x.
+    var = E[d^2] - E[d]^2 loses (E[d] / std)^2 of its relative precision: on x itself that is (mean / std)^2, up to 4e3 on the pooled
+    [mean | std] vectors BNRows normalises (docs/bn_train.md); on d it is ~1/8.  zhat = (d - E[d]) invstd and y = d scale + shift are
+    those of x; only the running mean needs c back (below)."""
+    lib, hctx = N.lib(), N.ctx(x.device)
+    dev, st = x.device, N.stream_ptr()
+    zeros, ones = _const(0.0, Cc, dev), _const(1.0, Cc, dev)
+    n = min(M, 8)
+    head = torch.empty((2, Cc), dtype=torch.float32, device=dev)
+    ws = _bytes(lib.vp_col_sums_workspace_bytes(M, Cc), dev)
+    _chk(lib.vp_col_sums_f32(hctx, x.data_ptr(), ldx, None, ldx, None, None, n, Cc, head.data_ptr(), ws.data_ptr(), ws.numel(), st), hctx)
+    negc = _affine_rows(head, Cc, 1, Cc, _const(-1.0 / n, Cc, dev), zeros, torch.empty(Cc, dtype=torch.float32, device=dev))
+    d = _affine_rows(x, ldx, M, Cc, ones, negc, torch.empty((M, Cc), dtype=torch.float32, device=dev))
+    sums = col_sums(d, d, zeros, ones)                     # [sum d | sum d^2]
+    mean, invstd, scale, shift = (torch.empty(Cc, dtype=torch.float32, device=dev) for _ in range(4))
+    _chk(lib.vp_bn_train_finalize(hctx, sums[0].data_ptr(), sums[1].data_ptr(), 1, M, Cc, gamma.data_ptr(), beta.data_ptr(), None,
+                                  run_var.data_ptr() if run_var is not None else None, momentum, eps, mean.data_ptr(),
+                                  invstd.data_ptr(), scale.data_ptr(), shift.data_ptr(), st), hctx)
+    if run_mean is not None:
+        # the running mean is that of x: sum x = sum d + M c.  It is blended by the finalize kernel itself (a second launch whose other
+        # outputs are scratch), because that kernel alone leaves the running statistics untouched while the context's bail-out word is set
+        mc = _affine_rows(head, Cc, 1, Cc, _const(float(M) / n, Cc, dev), zeros, torch.empty(Cc, dtype=torch.float32, device=dev))
+        sum_x = _affine_rows(sums, Cc, 1, Cc, ones, mc, torch.empty(Cc, dtype=torch.float32, device=dev))
+        scratch = torch.empty((4, Cc), dtype=torch.float32, device=dev)
+        _chk(lib.vp_bn_train_finalize(hctx, sum_x.data_ptr(), sums[1].data_ptr(), 1, M, Cc, None, None, run_mean.data_ptr(), None, momentum,
+                                      eps, scratch[0].data_ptr(), scratch[1].data_ptr(), scratch[2].data_ptr(), scratch[3].data_ptr(), st), hctx)
+    return d, negc, mean, invstd, scale, shift
+
+
 def _wide_bf16(M, Cin, Cout, KW, bias, rowbias, gamma, cfg):
     """Mixed precision, wide 1x1 TDNN blocks (tdnn1 / tdnn2 / MFA of ECAPA): the GEMM operands x and dz are kept as bf16 tensors --
     what the matrix cores would round them to anyway -- so the forward, data-gradient and weight-gradient kernels read half the
@@ -1225,26 +1264,22 @@ class MfaAspFn(torch.autograd.Function):
 class BNRows(torch.autograd.Function):
     """BatchNorm1D with batch statistics on a (M, C) tensor [-> ReLU].  With the ReLU, its backward is folded into the two
     BatchNorm-backward passes (they re-evaluate x * scale + shift > 0: vp_col_sums_masked_f32 / vp_bn_relu_bwd_masked_f32), so neither
-    the output nor a d(activation) tensor is kept (VPMI_BN_RELU_UNFOLDED=1: the three-pass form)."""
+    the output nor a d(activation) tensor is kept (VPMI_BN_RELU_UNFOLDED=1: the three-pass form).  C a multiple of 4.
+    Saved for backward is the CENTRED input d = x - center (bn_centred_stats): the backward's x - mean is d - E[d]."""
 
     @staticmethod
     def forward(ctx, x, gamma, beta, run_mean, run_var, momentum, eps, relu=False):
         lib, hctx = N.lib(), N.ctx(x.device)
         x = _f32c(x)
         M, Cc = x.shape
-        zeros, ones = _const(0.0, Cc, x.device), _const(1.0, Cc, x.device)
-        sums = col_sums(x, x, zeros, ones)                     # [sum x | sum x^2]
-        mean, invstd, scale, shift = (torch.empty(Cc, dtype=torch.float32, device=x.device) for _ in range(4))
-        _chk(lib.vp_bn_train_finalize(hctx, sums[0].data_ptr(), sums[1].data_ptr(), 1, M, Cc, gamma.data_ptr(), beta.data_ptr(),
-                                      run_mean.data_ptr() if run_mean is not None else None,
-                                      run_var.data_ptr() if run_var is not None else None, momentum, eps, mean.data_ptr(),
-                                      invstd.data_ptr(), scale.data_ptr(), shift.data_ptr(), N.stream_ptr()), hctx)
-        y = torch.empty_like(x)
-        _chk(lib.vp_affine_rows_f32(hctx, x.data_ptr(), Cc, scale.data_ptr(), shift.data_ptr(), M, Cc, y.data_ptr(), Cc, int(relu),
-                                    N.stream_ptr()), hctx)
-        fold = bool(relu) and Cc % 4 == 0 and not os.environ.get('VPMI_BN_RELU_UNFOLDED')
+        if Cc % 4:
+            raise N.VpmiError(f'BNRows: C = {Cc} is no multiple of 4 (the apply and backward passes are four channels wide)')
+        d, negc, mean, invstd, scale, shift = bn_centred_stats(x, Cc, M, Cc, gamma, beta, run_mean, run_var, momentum, eps)
+        y = _affine_rows(d, Cc, M, Cc, scale, shift, torch.empty_like(x), int(relu))
+        fold = bool(relu) and not os.environ.get('VPMI_BN_RELU_UNFOLDED')
         ctx.fold = (scale, shift) if fold else None
-        ctx.save_for_backward(x, mean, invstd, gamma, y if relu and not fold else None)
+        ctx.neg_center = negc                                  # the batch mean of x is the saved mean (of d) - neg_center
+        ctx.save_for_backward(d, mean, invstd, gamma, y if relu and not fold else None)
         return y
 
     @staticmethod
@@ -1817,25 +1852,17 @@ class CamDenseBlockFn(torch.autograd.Function):
             rm1, rv1, mom1, eps1, rm2, rv2, mom2, eps2, dil = bufs[l]
             Cl = C0 + l * G
             # nonlinear1: BatchNorm (batch statistics) -> ReLU over the first Cl columns, read where they are
-            zeros, ones = _const(0.0, Cl, dev), _const(1.0, Cl, dev)
-            sums = torch.empty((2, Cl), dtype=torch.float32, device=dev)
-            ws = _bytes(lib.vp_col_sums_workspace_bytes(M, Cl), dev)
-            _chk(lib.vp_col_sums_f32(hctx, X.data_ptr(), Cf, X.data_ptr(), Cf, zeros.data_ptr(), ones.data_ptr(), M, Cl, sums.data_ptr(),
-                                     ws.data_ptr(), ws.numel(), N.stream_ptr()), hctx)
-            mean, invstd, scale, shift = (torch.empty(Cl, dtype=torch.float32, device=dev) for _ in range(4))
-            _chk(lib.vp_bn_train_finalize(hctx, sums[0].data_ptr(), sums[1].data_ptr(), 1, M, Cl, g1.data_ptr(), be1.data_ptr(),
-                                          rm1.data_ptr() if rm1 is not None else None, rv1.data_ptr() if rv1 is not None else None, mom1, eps1,
-                                          mean.data_ptr(), invstd.data_ptr(), scale.data_ptr(), shift.data_ptr(), N.stream_ptr()), hctx)
-            h0 = torch.empty((M, Cl), dtype=torch.float32, device=dev)
-            _chk(lib.vp_affine_rows_f32(hctx, X.data_ptr(), Cf, scale.data_ptr(), shift.data_ptr(), M, Cl, h0.data_ptr(), Cl, 1,
-                                        N.stream_ptr()), hctx)
+            # (the same centred statistics as BNRows, which the per-layer form of this block runs here; d is formed again in backward)
+            d, negc, mean, invstd, scale, shift = bn_centred_stats(X, Cf, M, Cl, g1, be1, rm1, rv1, mom1, eps1)
+            h0 = _affine_rows(d, Cl, M, Cl, scale, shift, torch.empty((M, Cl), dtype=torch.float32, device=dev), 1)
+            del d
             t2, t3, t4 = _Tape((True,) * 9), _Tape((True,) * 8), _Tape((True,) * 8)
             # (linear1's bias sits directly in front of nonlinear2's BatchNorm: its gradient is identically zero, see Conv2dBlock.backward)
             z1 = ConvBlock.forward(t2, h0, wl1, bl1, None, None, None, None, None,
                                    dict(B=B, T=T, zero_bias_grad=not os.environ.get('VPMI_BN_BIAS_GRAD_SUMS')))
             h = BNRows.forward(t3, z1, g2, be2, rm2, rv2, mom2, eps2, True)
             CamLayerFn.forward(t4, h, wloc, bloc, w1, b1, w2, b2, dict(B=B, T=T, seg_len=seg_len, dilation=dil, out_into=X[:, Cl:Cl + G]))
-            tapes.append((Cl, mean, invstd, scale, shift, g1, t2, t3, t4))
+            tapes.append((Cl, mean, invstd, scale, shift, g1, t2, t3, t4, negc))
         ctx.tapes = tapes
         ctx.geom = (M, C0, G, L, Cf)
         ctx.save_for_backward(X)
@@ -1854,16 +1881,17 @@ class CamDenseBlockFn(torch.autograd.Function):
             Gb = g.clone()
         grads = [None] * (12 * L)
         for l in reversed(range(L)):
-            Cl, mean, invstd, scale, shift, g1, t2, t3, t4 = ctx.tapes[l]
+            Cl, mean, invstd, scale, shift, g1, t2, t3, t4, negc = ctx.tapes[l]
             r4 = CamLayerFn.backward(t4, Gb[:, Cl:Cl + G])
             r3 = BNRows.backward(t3, r4[0])
             r2 = _conv_block_bwd(t2, r3[0])
             dh0 = r2[0]
             sums = torch.empty((2, Cl), dtype=torch.float32, device=dev)
             ws = _bytes(lib.vp_col_sums_workspace_bytes(M, Cl), dev)
-            _chk(lib.vp_col_sums_masked_f32(hctx, dh0.data_ptr(), Cl, X.data_ptr(), Cf, mean.data_ptr(), invstd.data_ptr(), scale.data_ptr(),
+            d = _affine_rows(X, Cf, M, Cl, _const(1.0, Cl, dev), negc, torch.empty((M, Cl), dtype=torch.float32, device=dev))
+            _chk(lib.vp_col_sums_masked_f32(hctx, dh0.data_ptr(), Cl, d.data_ptr(), Cl, mean.data_ptr(), invstd.data_ptr(), scale.data_ptr(),
                                             shift.data_ptr(), 0.0, M, Cl, sums.data_ptr(), ws.data_ptr(), ws.numel(), N.stream_ptr()), hctx)
-            _chk(lib.vp_bn_relu_bwd_masked_f32(hctx, dh0.data_ptr(), Cl, X.data_ptr(), Cf, mean.data_ptr(), invstd.data_ptr(), g1.data_ptr(),
+            _chk(lib.vp_bn_relu_bwd_masked_f32(hctx, dh0.data_ptr(), Cl, d.data_ptr(), Cl, mean.data_ptr(), invstd.data_ptr(), g1.data_ptr(),
                                                sums.data_ptr(), scale.data_ptr(), shift.data_ptr(), 0.0, M, Cl, Gb.data_ptr(), Cf, 1,
                                                N.stream_ptr()), hctx)
             grads[12 * l:12 * l + 12] = [sums[1], sums[0], r2[1], r2[2], r3[1], r3[2], r4[1], r4[2], r4[3], r4[4], r4[5], r4[6]]
