@@ -1,4 +1,4 @@
-"""Oracle (CPU, float64 NumPy) of the BatchNorm training unit of csrc/train_ops.hip, and the inputs that put its kernels to work.
+"""Oracle (CPU, float64 NumPy) of the BatchNorm training unit of csrc/bn_train.hip, and the inputs that put its kernels to work.
 Test helper, not a test module; imports nothing of the engine.  docs/bn_train.md has the entry-point table and the bounds.
 
 Forward (utils.py:96-119, batch statistics over the M rows of a (M, C) tensor):
@@ -190,7 +190,7 @@ def rel_l2(a, ref):
 
 # ---------------------------------------------------------------------------------------------------- float32 restatements
 def colsum4_geometry(M, C4):
-    """csrc/train_ops.hip colsum4_geometry restated -> cl_shift, colblocks, rows per chunk, chunks (RG = 256 >> cl_shift row groups)."""
+    """csrc/bn_train.hip colsum4_geometry restated -> cl_shift, colblocks, rows per chunk, chunks (RG = 256 >> cl_shift row groups)."""
     cl_shift = 6 if C4 >= 64 else (5 if C4 >= 32 else 4)
     CL, RG = 1 << cl_shift, 256 >> cl_shift
     colblocks = (C4 + CL - 1) // CL

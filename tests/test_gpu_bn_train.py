@@ -1,4 +1,4 @@
-"""The BatchNorm training unit of csrc/train_ops.hip -- vp_bn_train_finalize, the vp_col_sums_* reductions, the vp_affine_rows_* apply
+"""The BatchNorm training unit of csrc/bn_train.hip -- vp_bn_train_finalize, the vp_col_sums_* reductions, the vp_affine_rows_* apply
 passes, the vp_bn_relu_bwd_* backward passes and their callers BNRows / ConvBlock / Conv2dBlock -- against the float64 oracle of
 tests/bn_oracle.py, entry point by entry point (docs/bn_train.md).  Run with -m gpu on an MI355X.
 

@@ -6,7 +6,8 @@ batch.  Run it on two checkouts (each with its own build), then compare the two 
     python tools/engine_bits.py --compare DIR_A DIR_B
     python tools/engine_bits.py --heads --out DIR    # instead: every output of the head / loss entry points (csrc/head.hip, head_tiled.hip, losses.hip)
     python tools/engine_bits.py --pooling --out DIR  # instead: every output of the pooling-statistics entry points (csrc/pooling_stats.hip)
-    python tools/engine_bits.py --time-b1            # 200 B = 1 forwards of ECAPA and ResNetSE per engine, GPU events (host launch overhead)
+    python tools/engine_bits.py --bn --out DIR       # instead: every output of the BatchNorm training unit (csrc/bn_train.hip), its Functions, one training step per backbone
+    python tools/engine_bits.py --time-b1           # 200 B = 1 forwards of ECAPA and ResNetSE per engine, GPU events (host launch overhead)
 """
 import argparse
 import itertools
@@ -271,6 +272,148 @@ def dump_pooling(out):
     print(f'{count} arrays, {blank} of them untouched or not finite (the refused bf16-logit calls at T > 320 leave theirs untouched)', flush=True)
 
 
+# --bn: the BatchNorm training unit (csrc/bn_train.hip, docs/bn_train.md)
+BN_C, BN_M, BN_UTT = (60, 132, 260), (1, 17, 257, 4097), ((9, 7), (65, 64))
+
+
+def dump_bn(out):
+    """(a) every entry point of the unit through ctypes, on the operands, pitches (contiguous; ld = C + 8 at column 4) and sentinel-framed
+    outputs of tests/test_gpu_bn_train.py, whose runners make the calls (VPMI_LIB picks the library); (b) one forward and backward of
+    BNRows / ConvBlock / Conv2dBlock / CamDenseBlockFn and one training step of every backbone: loss, parameter gradients, running
+    statistics (the Python side differs between two checkouts: run it from each).  bf16 outputs are saved as their bit patterns."""
+    import warnings
+    import torch
+    import ppvector
+    from ppvector import _native as N
+    from ppvector.models import _BUILT
+    from ppvector.models.campplus import CAMDenseTDNNBlock
+    from ppvector.train.campplus_train import dense_block
+    from ppvector.train.functions import BNRows, Conv2dBlock, ConvBlock, HeadLoss
+    from tests import bn_oracle as bo
+    from tests import test_gpu_bn_train as tb
+    warnings.simplefilter('ignore', RuntimeWarning)
+    os.makedirs(out, exist_ok=True)
+    lib, ctx = N.lib(), N.ctx(0)
+    count = blank = 0
+
+    def save(tag, bf16=(), **arrays):
+        nonlocal count, blank
+        torch.cuda.synchronize()
+        for k, v in arrays.items():
+            v = torch.as_tensor(v).detach().cpu()
+            blank += not bool(torch.isfinite(v.double()).all()) or bool((v == tb.SENTINEL).all())
+            # (the runners hand every output back as float64, exactly: a bf16 output goes back to its 16 bits)
+            v = v.to(torch.bfloat16).view(torch.int16) if k in bf16 else (v.float() if v.dtype == torch.float64 else v)
+            np.save(os.path.join(out, f'bn_{tag}.{k}.npy'), v.numpy())
+            count += 1
+
+    # ---- (a) entry points
+    for C, M, wide in itertools.product(BN_C, BN_M, (False, True)):
+        c, tag = tb.case(M, C), f'C{C}_M{M}' + ('_pitched' if wide else '')
+        save(f'{tag}_col_sums', f32=tb.run_col_sums(N, c, 'f32', wide), f32_one=tb.run_col_sums(N, c, 'f32', wide, two=False),
+             masked_hi0=tb.run_col_sums(N, c, 'masked', wide, mask_hi=0.0), masked_hi20=tb.run_col_sums(N, c, 'masked', wide, mask_hi=20.0),
+             b16=tb.run_col_sums(N, c, 'b16', wide))
+        for entry, relu_mask, use_gamma in itertools.product(('f32', 'bf16out', 'b16'), (0, 1), (False, True)):
+            dz, db = tb.run_dbias(N, c, entry, wide, relu_mask, use_gamma)[:2]
+            save(f'{tag}_dbias_{entry}_relu{relu_mask}_gamma{int(use_gamma)}', bf16=('dz',) if entry != 'f32' else (), dz=dz, dbias=db)
+        for relu_mask, use_gamma in itertools.product((0, 1), (False, True)):
+            save(f'{tag}_bwd_relu{relu_mask}_gamma{int(use_gamma)}', dz=tb.run_bwd(N, c, wide, False, relu_mask=relu_mask, use_gamma=use_gamma)[0])
+        for mask_hi, acc in itertools.product((0.0, 20.0), (0, 1)):
+            save(f'{tag}_bwd_masked_hi{int(mask_hi)}_acc{acc}', dz=tb.run_bwd(N, c, wide, True, mask_hi=mask_hi, accumulate=acc)[0])
+        for entry, relu in itertools.product(('f32', 'b16_f32', 'b16_b16', 'f32_b16'), (0, 1, 2)):
+            save(f'{tag}_affine_{entry}_relu{relu}', bf16=('y',) if entry.endswith('b16') else (), y=tb.run_affine(N, c, entry, wide, relu)[0])
+        sc, sh = tb.vec(c.ms), tb.vec(c.mh)
+        for with_add in (False, True):
+            zd, y, add, aux = tb.In(c.z, wide), tb.Out(M, C, True), tb.In(c.old, wide), tb.Out(M, C, wide)
+            N.check(lib.vp_affine_rows_aux_f32(ctx, zd.ptr, zd.ld, sc.data_ptr(), sh.data_ptr(), M, C, y.ptr, y.ld, add.ptr if with_add else None,
+                                               add.ld if with_add else 0, aux.ptr if with_add else None, aux.ld if with_add else 0,
+                                               N.stream_ptr()), ctx)
+            save(f'{tag}_affine_aux_add{int(with_add)}', y=y.get(), **({'aux': aux.get()} if with_add else {}))
+    for C, (B, T), wide in itertools.product(BN_C, BN_UTT, (False, True)):
+        c, tag = tb.case(B * T, C, T), f'C{C}_B{B}_T{T}' + ('_pitched' if wide else '')
+        save(f'{tag}_col_sums', utt=tb.run_col_sums(N, c, 'utt', wide), ctx=tb.run_col_sums(N, c, 'ctx', wide))
+        for entry, relu_mask, use_gamma in itertools.product(('utt', 'ctx'), (0, 1), (False, True)):
+            dz, db = tb.run_dbias(N, c, entry, wide, relu_mask, use_gamma)[:2]
+            save(f'{tag}_dbias_{entry}_relu{relu_mask}_gamma{int(use_gamma)}', bf16=('dz',), dz=dz, dbias=db)
+    for M in BN_M:                                     # C % 4 != 0: the one-channel col_sums_kernel
+        save(f'C6_M{M}_col_sums', f32=tb.run_col_sums(N, tb.case(M, 6), 'f32', False))
+    for C, nparts, i in itertools.product((6, 64, 260), (1, 17, 65, 1200), (0, 1)):
+        g = np.random.default_rng(31 * nparts + C)
+        ps = (g.standard_normal((nparts, C)) * 30 + 40).astype(np.float32)
+        pq = (g.uniform(0.5, 1.5, (nparts, C)) * (1000 / nparts) * 40 + (ps.astype(np.float64).sum(0) / 1000) ** 2 * 1000 / nparts).astype(np.float32)
+        gamma, beta, rm, rv = bo.affine_params(C, nparts)
+        if i:                                          # gamma / beta and the running pointers NULL
+            gamma = beta = rm = rv = None
+        names = ('mean', 'invstd', 'scale', 'shift', 'run_mean', 'run_var')
+        res = tb.run_finalize(N, ps, pq, 1000, C, gamma, beta, rm, rv, bo.MOM, bo.EPS)
+        save(f'C{C}_parts{nparts}_finalize_{"null" if i else "set"}', **{k: v for k, v in zip(names, res) if v is not None})
+    print(f'entry points: {count} arrays, {blank} of them untouched or not finite', flush=True)
+
+    # ---- (b) the Functions and the backbones' training steps
+    def fwd_bwd(tag, fn, inputs, seed):
+        """inputs: name -> f32 array that takes a gradient; fn(tensors) -> output"""
+        ts = {k: tb.vec(v).requires_grad_() for k, v in inputs.items()}
+        y = fn(ts)
+        dy = torch.from_numpy(np.random.default_rng(seed).standard_normal(tuple(y.shape)).astype(np.float32)).cuda()
+        y.backward(dy)
+        save(tag, y=y, **{f'd_{k}': t.grad for k, t in ts.items() if t.grad is not None})
+
+    for (M, C), relu in itertools.product(((17, 8), (48, 3072)), (False, True)):
+        gamma, beta, rm0, rv0 = bo.affine_params(C, M)
+        rm, rv = tb.vec(rm0), tb.vec(rv0)
+        fwd_bwd(f'BNRows_M{M}_C{C}_relu{int(relu)}', lambda t: BNRows.apply(t['x'], t['gamma'], t['beta'], rm, rv, 0.9, 1e-5, relu),
+                dict(x=bo.conditioned(M, C, 10), gamma=gamma, beta=beta), M + C)
+        save(f'BNRows_M{M}_C{C}_relu{int(relu)}', run_mean=rm, run_var=rv)
+    for T_out in (18, 19, 200):                        # 18: the separate column-sum pass; 19, 200: the conv's fused sums
+        B, Cin, Cout, kw = 4, 64, 64, 3
+        g = np.random.default_rng(T_out)
+        x = g.standard_normal((B * (T_out + kw - 1), Cin)).astype(np.float32)
+        w, bias = (g.standard_normal((Cout, Cin, kw)) / np.sqrt(Cin * kw)).astype(np.float32), g.standard_normal(Cout).astype(np.float32)
+        gamma, beta, rm0, rv0 = bo.affine_params(Cout, T_out)
+        rm, rv = tb.vec(rm0), tb.vec(rv0)
+        fwd_bwd(f'ConvBlock_T{T_out}', lambda t: ConvBlock.apply(t['x'], t['w'], t['bias'], None, t['gamma'], t['beta'], rm, rv,
+                                                                 dict(B=B, T=T_out + kw - 1, relu=True)),
+                dict(x=x, w=w, bias=bias, gamma=gamma, beta=beta), T_out)
+        save(f'ConvBlock_T{T_out}', run_mean=rm, run_var=rv)
+    for act in ('relu', 'hardtanh'):
+        B, T, Fq, Cin, Cout = 2, 9, 10, 8, 32
+        g = np.random.default_rng(len(act))
+        x, w = g.standard_normal((B * T * Fq, Cin)).astype(np.float32), (g.standard_normal((Cout, Cin, 3, 3)) * 2 / np.sqrt(Cin * 9)).astype(np.float32)
+        gamma, beta, rm0, rv0 = bo.affine_params(Cout, 3)
+        rm, rv = tb.vec(rm0), tb.vec(rv0)
+        fwd_bwd(f'Conv2dBlock_{act}', lambda t: Conv2dBlock.apply(t['x'], t['w'], t['bias'], t['gamma'], t['beta'], rm, rv, dict(B=B, T=T, F=Fq, act=act)),
+                dict(x=x, w=w, bias=g.standard_normal(Cout).astype(np.float32), gamma=gamma * 8, beta=beta + 6), 7)
+        save(f'Conv2dBlock_{act}', run_mean=rm, run_var=rv)
+    torch.manual_seed(77)
+    B, T = 3, 150
+    blk = CAMDenseTDNNBlock(num_layers=2, in_channels=128, out_channels=32, bn_channels=128, kernel_size=3).cuda().train()
+    x = torch.randn(B * T, 128, generator=torch.Generator().manual_seed(78)).cuda().requires_grad_()
+    y = dense_block([blk.tdnnd1, blk.tdnnd2], x, B, T)
+    y.backward(torch.randn(y.shape, generator=torch.Generator().manual_seed(79)).cuda())
+    save('CamDenseBlockFn', y=y, d_x=x.grad, **{'d_' + k: p.grad for k, p in blk.named_parameters()}, **dict(blk.named_buffers()))
+
+    def train_step(name, Bs, Ts, amp):
+        ppvector.set_train_amp(amp)
+        try:
+            torch.manual_seed(1234)
+            m = _BUILT[name](input_size=80).cuda().train()
+            g = torch.Generator().manual_seed(100 * Bs + Ts)
+            x, labels = torch.randn(Bs, Ts, 80, generator=g).cuda(), torch.randint(0, 67, (Bs,), generator=g).cuda()
+            emb = m(x)
+            W = (torch.randn(emb.shape[1], 67, generator=g) * 0.1).cuda().requires_grad_()
+            loss = HeadLoss.apply(emb, W, labels, 0.2, 32.0, 0.0, False)[0]
+            loss.backward()
+            save(f'step_{name}_{"amp" if amp else "f32"}_B{Bs}_T{Ts}', loss=loss, emb=emb, d_head=W.grad,
+                 **{'d_' + k: p.grad for k, p in m.named_parameters() if p.grad is not None}, **dict(m.named_buffers()))
+        finally:
+            ppvector.set_train_amp(False)
+
+    for name, _ in MODELS:
+        train_step(name, 4, 100, False)
+    train_step('EcapaTdnn', 16, 298, True)             # the wide bf16 layers (the b16 / utt / ctx forms) need M >= 4096
+    print(f'{count} arrays, {blank} of them untouched or not finite', flush=True)
+
+
 def _ulps(x, y):
     """Largest distance of two f32 arrays in units in the last place (inf where a NaN or the shapes differ)."""
     if x.shape != y.shape or x.dtype != np.float32 or np.isnan(x).any() or np.isnan(y).any():
@@ -330,6 +473,7 @@ if __name__ == '__main__':
     ap.add_argument('--time-b1', action='store_true')
     ap.add_argument('--heads', action='store_true')
     ap.add_argument('--pooling', action='store_true')
+    ap.add_argument('--bn', action='store_true')
     a = ap.parse_args()
     if a.compare:
         sys.exit(1 if compare(*a.compare) else 0)
@@ -339,5 +483,7 @@ if __name__ == '__main__':
         dump_heads(a.out)
     elif a.out and a.pooling:
         dump_pooling(a.out)
+    elif a.out and a.bn:
+        dump_bn(a.out)
     elif a.out:
         dump(a.out, a.only, a.suffix)

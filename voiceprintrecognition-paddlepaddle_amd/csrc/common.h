@@ -64,6 +64,11 @@ static inline const unsigned* vp_fault_word(const vp_ctx* ctx) { return ctx && c
     } while (0)
 
 static inline size_t vp_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+// workgroups of 256 threads for a grid-stride loop over `total` items, at most 256 x 64 of them
+static inline unsigned grid1d(long long total) {
+    long long b = (total + 255) / 256;
+    return (unsigned)(b > 256 * 64 ? 256 * 64 : (b < 1 ? 1 : b));
+}
 
 typedef __bf16 bf16_t;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -127,6 +132,10 @@ int vp_run_asp(vp_ctx* ctx, const vp_asp_weights& A, int dtype, const void* x, i
                int B, int T, const VpAspBufs& w, hipStream_t st);
 int vp_asp_utt_bf16(vp_ctx* ctx, const void* x, int ldx, const vp_tdnn_layer* tdnn, const float* rowbias, const void* conv_w,
                     const float* conv_b, int B, int T, int C, int att, float eps, float* pooled, hipStream_t st);
+// out[n] = sum over S partial arrays part[S][n] in fixed order (train_ops.hip; the weight gradient's [Cout][K] layouts via Cin / KW / KF,
+// the column sums and bias gradients of bn_train.hip with the defaults)
+void vp_launch_sum_partials(const float* part, int S, long long n, float* out, hipStream_t st, int Cin = 1, int KW = 1, int batch = 1,
+                            int KF = 1);
 int vp_wgrad_tr256_splits(long long M, int N, int K);
 int vp_wgrad_tr256_bf16(vp_ctx* ctx, const void* x, int ldx, int xoff, const void* dz, int lddz, long long M, int N, int K, float* part,
                         int* splits_out, hipStream_t st);

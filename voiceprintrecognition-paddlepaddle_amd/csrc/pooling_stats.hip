@@ -513,7 +513,7 @@ __global__ __launch_bounds__(256) void time_stats_bwd_kernel(TsBwdArgs a) {
 
 // The same gradient as per-utterance coefficients: dx[b,t,c] = alpha[b,c] + beta[b,c] * x[b,t,c] with beta = [var > eps] dstd / (std T),
 // alpha = dmean / T - beta * mean -- what the BatchNorm-backward passes of the producing layer add to their d y on the fly
-// (ColSum4Args UTT == 2, csrc/train_ops.hip) instead of a pass over the (B*T, C) tensor.  ab: [2][B][C]
+// (ColSum4Args UTT == 2, csrc/bn_train.hip) instead of a pass over the (B*T, C) tensor.  ab: [2][B][C]
 __global__ __launch_bounds__(256) void time_stats_bwd_coeffs_kernel(const float* stats, const float* dstats, int B, int C, int T, float eps, float* ab) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= B * C) return;

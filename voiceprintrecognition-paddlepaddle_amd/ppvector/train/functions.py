@@ -81,23 +81,149 @@ def _conv_desc(x, B, T_in, T_out, Cin, Cout, KW, dil, pad_mode, pad_left, w, bia
     return d
 
 
+def _act_bwd(act, dy, y):
+    """-> d(input) of the activation `act` (VP_ACT_*) from its output gradient dy and the tensor y its backward reads (f32, same shape)"""
+    lib, hctx = N.lib(), N.ctx(dy.device)
+    t = torch.empty_like(dy)
+    _chk(lib.vp_act_bwd_f32(hctx, act, dy.data_ptr(), y.data_ptr(), dy.numel(), t.data_ptr(), N.stream_ptr()), hctx)
+    return t
+
+
+# ---------------------------------------------------------------------------------------------- the BatchNorm training unit
+# Every call of csrc/bn_train.hip (vp_col_sums_*, vp_bn_train_finalize, vp_affine_rows_*, vp_bn_relu_bwd_*) is made here; the Functions
+# below say what they want and call these.  Contracts and measured error: docs/bn_train.md.  Each helper allocates what it returns and
+# its workspace and launches on the current stream, nothing else: safe under a stream capture the way _const is.
+# mask = (ms, mh, hi): an activation BEHIND the BatchNorm folded into its backward -- d y counts only where 0 < z ms + mh [< hi; 0: no
+# upper bound].  utt: the per-utterance term on the output gradient that _conv_block_bwd documents (bf16 z only).
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _col_sums(a, lda, M, Cc, b=None, bmean=None, bscale=None, mask=None, utt=None):
+    """-> (2, Cc) f32 [sum_m a | sum_m a (b - bmean) bscale] over the M rows at a (f32, row pitch lda); b (M, Cc) contiguous, f32 or bf16.
+    With a mask, None when the library cannot take the operands four channels wide (VP_EUNSUP): the caller materialises the mask."""
+    lib, hctx = N.lib(), N.ctx(a.device)
+    sums = torch.empty((2, Cc), dtype=torch.float32, device=a.device)
+    ws = _bytes(lib.vp_col_sums_workspace_bytes(M, Cc), a.device)
+    head, bstat = (hctx, a.data_ptr(), lda), (_ptr(b), Cc, _ptr(bmean), _ptr(bscale))
+    tail = (M, Cc, sums.data_ptr(), ws.data_ptr(), ws.numel(), N.stream_ptr())
+    if mask is not None:
+        rc = lib.vp_col_sums_masked_f32(*head, *bstat, mask[0].data_ptr(), mask[1].data_ptr(), mask[2], *tail)
+        if rc == N.VP_EUNSUP:
+            return None
+    elif b is None or b.dtype != torch.bfloat16:
+        rc = lib.vp_col_sums_f32(*head, *bstat, *tail)
+    elif utt is None:
+        rc = lib.vp_col_sums_f32_b16(*head, *bstat, *tail)
+    elif utt[0] == 'ctx':
+        _, al, be, Tu, bsc, bsh = utt
+        rc = lib.vp_col_sums_f32_b16_ctx(*head, al.data_ptr(), be.data_ptr(), int(Tu), bsc.data_ptr(), bsh.data_ptr(), *bstat, *tail)
+    else:
+        rc = lib.vp_col_sums_f32_b16_utt(*head, utt[1].data_ptr(), utt[2].data_ptr(), int(utt[3]), *bstat, *tail)
+    _chk(rc, hctx)
+    return sums
+
+
 def col_sums(a, b=None, bmean=None, bscale=None):
     """-> (2, C): sum_m a and (when b) sum_m a * (b - bmean) * bscale."""
-    lib, ctx = N.lib(), N.ctx(a.device)
-    M, Cc = a.shape
-    out = torch.empty((2, Cc), dtype=torch.float32, device=a.device)
-    ws = _bytes(lib.vp_col_sums_workspace_bytes(M, Cc), a.device)
-    _chk(lib.vp_col_sums_f32(ctx, a.data_ptr(), Cc, b.data_ptr() if b is not None else None, Cc,
-                             bmean.data_ptr() if b is not None else None, bscale.data_ptr() if b is not None else None,
-                             M, Cc, out.data_ptr(), ws.data_ptr(), ws.numel(), N.stream_ptr()), ctx)
+    return _col_sums(a, a.shape[1], a.shape[0], a.shape[1], b, bmean, bscale)
+
+
+def _raw_sums(z):
+    """-> (2, C) [sum z | sum z^2] of an f32 (M, C) tensor: the statistics pass of a BatchNorm whose conv did not fuse its sums"""
+    return col_sums(z, z, _const(0.0, z.shape[1], z.device), _const(1.0, z.shape[1], z.device))
+
+
+def _bn_finalize(psum, psumsq, nparts, M, Cc, gamma, beta, run_mean, run_var, momentum, eps):
+    """-> mean, invstd, scale (= gamma invstd), shift (= beta - mean scale) from nparts rows of partial sums; the running statistics
+    that are given are blended in place (gamma, beta, run_mean, run_var may each be None)."""
+    lib, hctx = N.lib(), N.ctx(psum.device)
+    mean, invstd, scale, shift = (torch.empty(Cc, dtype=torch.float32, device=psum.device) for _ in range(4))
+    _chk(lib.vp_bn_train_finalize(hctx, psum.data_ptr(), psumsq.data_ptr(), nparts, M, Cc, _ptr(gamma), _ptr(beta), _ptr(run_mean),
+                                  _ptr(run_var), momentum, eps, mean.data_ptr(), invstd.data_ptr(), scale.data_ptr(), shift.data_ptr(),
+                                  N.stream_ptr()), hctx)
+    return mean, invstd, scale, shift
+
+
+def _affine_rows(z, ldz, rows, Cc, scale, shift, out=None, relu=0, dtype=torch.float32):
+    """The apply pass: out (rows, Cc, contiguous; made here as `dtype` unless given) = z * scale + shift [relu 1: -> ReLU, 2: ->
+    Hardtanh(0, 20)]; z f32 or bf16, read with row pitch ldz"""
+    lib, hctx = N.lib(), N.ctx(z.device)
+    if out is None:
+        out = torch.empty((rows, Cc), dtype=dtype, device=z.device)
+    b16 = torch.bfloat16
+    fn = ((lib.vp_affine_rows_b16_b16 if out.dtype == b16 else lib.vp_affine_rows_b16_f32) if z.dtype == b16 else
+          (lib.vp_affine_rows_f32_b16 if out.dtype == b16 else lib.vp_affine_rows_f32))
+    _chk(fn(hctx, z.data_ptr(), ldz, scale.data_ptr(), shift.data_ptr(), rows, Cc, out.data_ptr(), Cc, relu, N.stream_ptr()), hctx)
     return out
 
 
-def _affine_rows(z, ldz, rows, Cc, scale, shift, out, relu=0):
-    """out (rows, Cc, contiguous) = z * scale + shift [-> ReLU]; z read with row pitch ldz"""
-    lib, hctx = N.lib(), N.ctx(out.device)
-    _chk(lib.vp_affine_rows_f32(hctx, z.data_ptr(), ldz, scale.data_ptr(), shift.data_ptr(), rows, Cc, out.data_ptr(), Cc, relu, N.stream_ptr()), hctx)
-    return out
+def _affine_rows_aux(z, scale, shift, into=None, add=None):
+    """-> y, aux: y = z * scale + shift written into `into` (a column slice of a wider f32 tensor) when given, and aux = y + add (add:
+    such a slice too) when add is given, from the same pass"""
+    lib, hctx = N.lib(), N.ctx(z.device)
+    M, Cc = z.shape
+    y = into if into is not None else torch.empty_like(z)
+    aux = torch.empty_like(z) if add is not None else None
+    _chk(lib.vp_affine_rows_aux_f32(hctx, z.data_ptr(), Cc, scale.data_ptr(), shift.data_ptr(), M, Cc, y.data_ptr(), y.stride(0), _ptr(add),
+                                    add.stride(0) if add is not None else 0, _ptr(aux), Cc, N.stream_ptr()), hctx)
+    return y, aux
+
+
+def _bn_bwd_dz(dy, z, mean, invstd, gamma, sums, relu_mask=0, mask=None, dst=None, accumulate=False, want_dbias=False, bf16_out=False,
+               utt=None):
+    """-> dz, dbias.  dz = [relu_mask: z > 0] gamma invstd (dy - sums[0] / M - zhat sums[1] / M) of (M, C) contiguous dy (f32) and z (f32 /
+    bf16).  With a mask: into the first C columns of dst (its own row pitch; accumulate: dz +=) when given.  want_dbias: dbias = sum_m dz
+    from the same pass (else None); bf16_out: dz as bf16."""
+    lib, hctx = N.lib(), N.ctx(z.device)
+    M, Cc = z.shape
+    head = (hctx, dy.data_ptr(), Cc)
+    stats = (z.data_ptr(), Cc, mean.data_ptr(), invstd.data_ptr(), _ptr(gamma), sums.data_ptr())
+    if mask is not None:
+        dz = dst if dst is not None else torch.empty_like(dy)
+        _chk(lib.vp_bn_relu_bwd_masked_f32(*head, *stats, mask[0].data_ptr(), mask[1].data_ptr(), mask[2], M, Cc, dz.data_ptr(), dz.stride(0),
+                                           int(accumulate), N.stream_ptr()), hctx)
+        return dz, None
+    dz = torch.empty_like(dy, dtype=torch.bfloat16 if bf16_out else torch.float32)
+    if not want_dbias:
+        _chk(lib.vp_bn_relu_bwd_f32(*head, *stats, M, Cc, int(relu_mask), dz.data_ptr(), Cc, N.stream_ptr()), hctx)
+        return dz, None
+    dbias = torch.empty(Cc, dtype=torch.float32, device=z.device)
+    ws = _bytes(lib.vp_bn_relu_bwd_dbias_workspace_bytes(M, Cc), z.device)
+    tail = (M, Cc, int(relu_mask), dz.data_ptr(), Cc, dbias.data_ptr(), ws.data_ptr(), ws.numel(), N.stream_ptr())
+    if utt is None:
+        fn = (lib.vp_bn_relu_bwd_dbias_b16 if z.dtype == torch.bfloat16 else
+              lib.vp_bn_relu_bwd_dbias_bf16out if bf16_out else lib.vp_bn_relu_bwd_dbias_f32)
+        rc = fn(*head, *stats, *tail)
+    elif utt[0] == 'ctx':
+        _, al, be, Tu, bsc, bsh = utt
+        rc = lib.vp_bn_relu_bwd_dbias_b16_ctx(*head, al.data_ptr(), be.data_ptr(), int(Tu), bsc.data_ptr(), bsh.data_ptr(), *stats, *tail)
+    else:
+        rc = lib.vp_bn_relu_bwd_dbias_b16_utt(*head, utt[1].data_ptr(), utt[2].data_ptr(), int(utt[3]), *stats, *tail)
+    _chk(rc, hctx)
+    return dz, dbias
+
+
+def _bn_bwd(dy, z, mean, invstd, gamma):
+    """The plain BatchNorm backward of (M, C) f32 tensors -> dz, sums ([dbeta | dgamma])"""
+    sums = col_sums(dy, z, mean, invstd)
+    return _bn_bwd_dz(dy, z, mean, invstd, gamma, sums)[0], sums
+
+
+def _bn_act_bwd(dy, z, mean, invstd, gamma, mask, dst=None, accumulate=False):
+    """BatchNorm -> ReLU / Hardtanh(0, 20) backward with the activation's mask folded into the two passes -> dz, sums ([dbeta | dgamma]);
+    dst, accumulate: see _bn_bwd_dz.  A d y the masked reduction cannot take (storage at a 4-byte offset; docs/bn_train.md) goes the
+    plain way: the activation's output is formed again, its backward applied to d y, then the unmasked passes."""
+    M, Cc = z.shape
+    sums = _col_sums(dy, Cc, M, Cc, z, mean, invstd, mask=mask)
+    if sums is not None:
+        return _bn_bwd_dz(dy, z, mean, invstd, gamma, sums, mask=mask, dst=dst, accumulate=accumulate)[0], sums
+    if dst is not None:
+        raise N.VpmiError('BatchNorm backward: a misaligned gradient cannot be folded into a shared gradient buffer')
+    ms, mh, hi = mask
+    yr = _affine_rows(z, Cc, M, Cc, ms, mh, relu=2 if hi else 1)
+    return _bn_bwd(_act_bwd(N.VP_ACT_HARDTANH20 if hi else N.VP_ACT_RELU, dy, yr), z, mean, invstd, gamma)
 
 
 def bn_centred_stats(x, ldx, M, Cc, gamma, beta, run_mean, run_var, momentum, eps):
@@ -107,28 +233,21 @@ def bn_centred_stats(x, ldx, M, Cc, gamma, beta, run_mean, run_var, momentum, ep
     var = E[d^2] - E[d]^2 loses (E[d] / std)^2 of its relative precision: on x itself that is (mean / std)^2, up to 4e3 on the pooled
     [mean | std] vectors BNRows normalises (docs/bn_train.md); on d it is ~1/8.  zhat = (d - E[d]) invstd and y = d scale + shift are
     those of x; only the running mean needs c back (below)."""
-    lib, hctx = N.lib(), N.ctx(x.device)
-    dev, st = x.device, N.stream_ptr()
+    dev = x.device
     zeros, ones = _const(0.0, Cc, dev), _const(1.0, Cc, dev)
     n = min(M, 8)
-    head = torch.empty((2, Cc), dtype=torch.float32, device=dev)
-    ws = _bytes(lib.vp_col_sums_workspace_bytes(M, Cc), dev)
-    _chk(lib.vp_col_sums_f32(hctx, x.data_ptr(), ldx, None, ldx, None, None, n, Cc, head.data_ptr(), ws.data_ptr(), ws.numel(), st), hctx)
-    negc = _affine_rows(head, Cc, 1, Cc, _const(-1.0 / n, Cc, dev), zeros, torch.empty(Cc, dtype=torch.float32, device=dev))
-    d = _affine_rows(x, ldx, M, Cc, ones, negc, torch.empty((M, Cc), dtype=torch.float32, device=dev))
+    vec = lambda: torch.empty(Cc, dtype=torch.float32, device=dev)
+    head = _col_sums(x, ldx, n, Cc)
+    negc = _affine_rows(head, Cc, 1, Cc, _const(-1.0 / n, Cc, dev), zeros, vec())
+    d = _affine_rows(x, ldx, M, Cc, ones, negc)
     sums = col_sums(d, d, zeros, ones)                     # [sum d | sum d^2]
-    mean, invstd, scale, shift = (torch.empty(Cc, dtype=torch.float32, device=dev) for _ in range(4))
-    _chk(lib.vp_bn_train_finalize(hctx, sums[0].data_ptr(), sums[1].data_ptr(), 1, M, Cc, gamma.data_ptr(), beta.data_ptr(), None,
-                                  run_var.data_ptr() if run_var is not None else None, momentum, eps, mean.data_ptr(),
-                                  invstd.data_ptr(), scale.data_ptr(), shift.data_ptr(), st), hctx)
+    mean, invstd, scale, shift = _bn_finalize(sums[0], sums[1], 1, M, Cc, gamma, beta, None, run_var, momentum, eps)
     if run_mean is not None:
         # the running mean is that of x: sum x = sum d + M c.  It is blended by the finalize kernel itself (a second launch whose other
         # outputs are scratch), because that kernel alone leaves the running statistics untouched while the context's bail-out word is set
-        mc = _affine_rows(head, Cc, 1, Cc, _const(float(M) / n, Cc, dev), zeros, torch.empty(Cc, dtype=torch.float32, device=dev))
-        sum_x = _affine_rows(sums, Cc, 1, Cc, ones, mc, torch.empty(Cc, dtype=torch.float32, device=dev))
-        scratch = torch.empty((4, Cc), dtype=torch.float32, device=dev)
-        _chk(lib.vp_bn_train_finalize(hctx, sum_x.data_ptr(), sums[1].data_ptr(), 1, M, Cc, None, None, run_mean.data_ptr(), None, momentum,
-                                      eps, scratch[0].data_ptr(), scratch[1].data_ptr(), scratch[2].data_ptr(), scratch[3].data_ptr(), st), hctx)
+        mc = _affine_rows(head, Cc, 1, Cc, _const(float(M) / n, Cc, dev), zeros, vec())
+        sum_x = _affine_rows(sums, Cc, 1, Cc, ones, mc, vec())
+        _bn_finalize(sum_x, sums[1], 1, M, Cc, None, None, run_mean, None, momentum, eps)
     return d, negc, mean, invstd, scale, shift
 
 
@@ -315,18 +434,14 @@ class ConvBlock(torch.autograd.Function):
         if bn and ps is None and wide >= 2:
             raise N.VpmiError('ConvBlock: bf16 pre-BN activation needs the conv\'s fused column sums (utterances of >= ~19 frames)')
         if bn and ps is None:                                   # very short utterances: a separate column-sum pass
-            zeros, ones = _const(0.0, Cout, x.device), _const(1.0, Cout, x.device)
-            sums = col_sums(z, z, zeros, ones)
+            sums = _raw_sums(z)
             ps, pq = sums[0:1], sums[1:2]
         mean = invstd = None
         y = z
         if bn:
-            mean, invstd, scale, shift = (torch.empty(Cout, dtype=torch.float32, device=x.device) for _ in range(4))
-            _chk(lib.vp_bn_train_finalize(hctx, ps.data_ptr(), pq.data_ptr(), ps.shape[0], B * T_out, Cout, gamma.data_ptr(),
-                                          beta.data_ptr(), run_mean.data_ptr() if run_mean is not None else None,
-                                          run_var.data_ptr() if run_var is not None else None, cfg.get('momentum', 0.9),
-                                          cfg.get('eps', 1e-5), mean.data_ptr(), invstd.data_ptr(), scale.data_ptr(),
-                                          shift.data_ptr(), N.stream_ptr()), hctx)
+            M = B * T_out
+            mean, invstd, scale, shift = _bn_finalize(ps, pq, ps.shape[0], M, Cout, gamma, beta, run_mean, run_var, cfg.get('momentum', 0.9),
+                                                      cfg.get('eps', 1e-5))
             into, add = cfg.get('y_into'), cfg.get('aux_add')
             y16 = wide >= 2 and cfg.get('y_bf16') and not tanh
             if y16 and cfg.get('_no_apply'):
@@ -335,39 +450,23 @@ class ConvBlock(torch.autograd.Function):
                 cfg['_zaff'] = (z, scale, shift)
             elif y16:
                 # the output's only consumer reads it as bf16 and takes its time statistics from the fused sums (ECAPA's MFA -> ASP):
-                # 234 MB written instead of 469, and every later pass over it reads half
-                y16t = torch.empty(z.shape, dtype=torch.bfloat16, device=x.device)
-                _chk(lib.vp_affine_rows_b16_b16(hctx, z.data_ptr(), Cout, scale.data_ptr(), shift.data_ptr(), B * T_out, Cout,
-                                                y16t.data_ptr(), Cout, 0, N.stream_ptr()), hctx)
-                # autograd hands a tensor's gradient over in the tensor's dtype: a bf16 y would get its 469 MB f32 gradient cast down.
+                # 234 MB written instead of 469, and every later pass over it reads half.
+                # Autograd hands a tensor's gradient over in the tensor's dtype: a bf16 y would get its 469 MB f32 gradient cast down.
                 # The tape therefore sees an f32 PLACEHOLDER of the right shape that owns no memory (one zero, expanded); the values
                 # travel as its bf16 twin, the way producers' twins do everywhere else (`_vp_bf16`), marked as the only copy.
+                cfg['_y16'] = _affine_rows(z, Cout, M, Cout, scale, shift, dtype=torch.bfloat16)
                 y = _placeholder(z.shape, x.device)
-                cfg['_y16'] = y16t
-            elif wide >= 2:
-                y = torch.empty(z.shape, dtype=torch.float32, device=x.device)
-                _chk(lib.vp_affine_rows_b16_f32(hctx, z.data_ptr(), Cout, scale.data_ptr(), shift.data_ptr(), B * T_out, Cout,
-                                                y.data_ptr(), Cout, 0, N.stream_ptr()), hctx)
+            elif wide >= 2:                                     # f32 y from the bf16 z
+                y = _affine_rows(z, Cout, M, Cout, scale, shift)
             elif into is not None or add is not None:
                 # y straight into a channel slice of a wider tensor, and aux = y + add (the next Res2Net chunk's input) in the same pass
-                y = into if into is not None else torch.empty_like(z)
-                aux = torch.empty_like(z) if add is not None else None
-                _chk(lib.vp_affine_rows_aux_f32(hctx, z.data_ptr(), Cout, scale.data_ptr(), shift.data_ptr(), B * T_out, Cout,
-                                                y.data_ptr(), y.stride(0), add.data_ptr() if add is not None else None,
-                                                add.stride(0) if add is not None else 0, aux.data_ptr() if aux is not None else None,
-                                                Cout, N.stream_ptr()), hctx)
-                ctx.aux_out = aux
+                y, ctx.aux_out = _affine_rows_aux(z, scale, shift, into, add)
             elif cfg.get('y_bf16') and not wide and not tanh and ppvector.get_train_amp():
                 # a layer outside the wide set whose consumers read bf16 only (ECAPA's block 0): the apply pass writes the bf16 form directly
-                y16t = torch.empty(z.shape, dtype=torch.bfloat16, device=x.device)
-                _chk(lib.vp_affine_rows_f32_b16(hctx, z.data_ptr(), Cout, scale.data_ptr(), shift.data_ptr(), B * T_out, Cout,
-                                                y16t.data_ptr(), Cout, 0, N.stream_ptr()), hctx)
+                cfg['_y16'] = _affine_rows(z, Cout, M, Cout, scale, shift, dtype=torch.bfloat16)
                 y = _placeholder(z.shape, x.device)
-                cfg['_y16'] = y16t
             else:
-                y = torch.empty_like(z)
-                _chk(lib.vp_affine_rows_f32(hctx, z.data_ptr(), Cout, scale.data_ptr(), shift.data_ptr(), B * T_out, Cout,
-                                            y.data_ptr(), Cout, 0, N.stream_ptr()), hctx)
+                y = _affine_rows(z, Cout, M, Cout, scale, shift)
         if tanh:
             yt = torch.empty_like(y)
             _chk(lib.vp_act_f32(hctx, tanh, y.data_ptr(), y.numel(), yt.data_ptr(), N.stream_ptr()), hctx)
@@ -412,68 +511,25 @@ def _conv_block_bwd(ctx, dy, skip=None, fold=None, utt=None):
     else:
         dy = _f32c(dy)
     if tanh:
-        t = torch.empty_like(dy)
-        _chk(lib.vp_act_bwd_f32(hctx, tanh, dy.data_ptr(), yt.data_ptr(), dy.numel(), t.data_ptr(), N.stream_ptr()), hctx)
-        dy = t
+        dy = _act_bwd(tanh, dy, yt)
     dgamma = dbeta = None
     if bn or relu:
         if utt is not None and not (bn and z.dtype == torch.bfloat16 and has_bias and Cout % 4 == 0 and not tanh):
             raise N.VpmiError('ConvBlock backward: a per-utterance term on the output gradient needs the bf16 pre-BatchNorm form')
         if bn:
-            if z.dtype == torch.bfloat16 and utt is not None and utt[0] == 'ctx':
-                # d y = dy + alpha[b] + beta[b] * y: a consumer's context-statistics gradient (MfaAspFn), y re-formed from z
-                _, al, be, Tu, bsc, bsh = utt
-                sums = torch.empty((2, Cout), dtype=torch.float32, device=dev)
-                ws = _bytes(lib.vp_col_sums_workspace_bytes(M, Cout), dev)
-                _chk(lib.vp_col_sums_f32_b16_ctx(hctx, dy.data_ptr(), Cout, al.data_ptr(), be.data_ptr(), int(Tu), bsc.data_ptr(), bsh.data_ptr(),
-                                                 z.data_ptr(), Cout, mean.data_ptr(), invstd.data_ptr(), M, Cout, sums.data_ptr(), ws.data_ptr(),
-                                                 ws.numel(), N.stream_ptr()), hctx)
-            elif z.dtype == torch.bfloat16 and utt is not None:
-                # d y = dy * s[b] + dm[b] / T: the SE block behind this conv (ConvSEFn)
-                sums = torch.empty((2, Cout), dtype=torch.float32, device=dev)
-                ws = _bytes(lib.vp_col_sums_workspace_bytes(M, Cout), dev)
-                _chk(lib.vp_col_sums_f32_b16_utt(hctx, dy.data_ptr(), Cout, utt[1].data_ptr(), utt[2].data_ptr(), int(utt[3]), z.data_ptr(), Cout,
-                                                 mean.data_ptr(), invstd.data_ptr(), M, Cout, sums.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                 N.stream_ptr()), hctx)
-            elif z.dtype == torch.bfloat16:
-                sums = torch.empty((2, Cout), dtype=torch.float32, device=dev)
-                ws = _bytes(lib.vp_col_sums_workspace_bytes(M, Cout), dev)
-                _chk(lib.vp_col_sums_f32_b16(hctx, dy.data_ptr(), Cout, z.data_ptr(), Cout, mean.data_ptr(), invstd.data_ptr(), M, Cout,
-                                             sums.data_ptr(), ws.data_ptr(), ws.numel(), N.stream_ptr()), hctx)
-            else:
-                sums = col_sums(dy, z, mean, invstd)
+            # with utt the two passes form d y on the fly: ('se', ...) dy * s[b] + dm[b] / T (ConvSEFn), ('ctx', ...) dy + alpha[b] + beta[b] * y,
+            # y re-formed from z (MfaAspFn)
+            sums = _col_sums(dy, Cout, M, Cout, z, mean, invstd, utt=utt)
             dgamma, dbeta = sums[1], sums[0]             # views of a buffer this call owns: no copies
             mu, istd, g = mean, invstd, gamma
         else:                                   # ReLU alone: the BN backward formula with identity statistics
             sums = torch.zeros((2, Cout), dtype=torch.float32, device=dev)
             mu, istd = _const(0.0, Cout, dev), _const(1.0, Cout, dev)
             g = None
-        dz = torch.empty_like(dy, dtype=torch.bfloat16 if wide else torch.float32)
-        if has_bias and Cout % 4 == 0:          # the bias gradient (column sums of dz) from the pass that writes dz
-            dbias = torch.empty(Cout, dtype=torch.float32, device=dev)
-            ws = _bytes(lib.vp_bn_relu_bwd_dbias_workspace_bytes(M, Cout), dev)
-            fn = (lib.vp_bn_relu_bwd_dbias_b16 if z.dtype == torch.bfloat16 else
-                  lib.vp_bn_relu_bwd_dbias_bf16out if wide else lib.vp_bn_relu_bwd_dbias_f32)
-            if utt is not None and utt[0] == 'ctx':
-                _, al, be, Tu, bsc, bsh = utt
-                _chk(lib.vp_bn_relu_bwd_dbias_b16_ctx(hctx, dy.data_ptr(), Cout, al.data_ptr(), be.data_ptr(), int(Tu), bsc.data_ptr(), bsh.data_ptr(),
-                                                      z.data_ptr(), Cout, mu.data_ptr(), istd.data_ptr(), g.data_ptr() if g is not None else None,
-                                                      sums.data_ptr(), M, Cout, int(relu), dz.data_ptr(), Cout, dbias.data_ptr(),
-                                                      ws.data_ptr(), ws.numel(), N.stream_ptr()), hctx)
-            elif utt is not None:
-                _chk(lib.vp_bn_relu_bwd_dbias_b16_utt(hctx, dy.data_ptr(), Cout, utt[1].data_ptr(), utt[2].data_ptr(), int(utt[3]), z.data_ptr(),
-                                                      Cout, mu.data_ptr(), istd.data_ptr(), g.data_ptr() if g is not None else None,
-                                                      sums.data_ptr(), M, Cout, int(relu), dz.data_ptr(), Cout, dbias.data_ptr(),
-                                                      ws.data_ptr(), ws.numel(), N.stream_ptr()), hctx)
-            else:
-                _chk(fn(hctx, dy.data_ptr(), Cout, z.data_ptr(), Cout, mu.data_ptr(), istd.data_ptr(),
-                        g.data_ptr() if g is not None else None, sums.data_ptr(), M, Cout, int(relu),
-                        dz.data_ptr(), Cout, dbias.data_ptr(), ws.data_ptr(), ws.numel(), N.stream_ptr()), hctx)
-        else:
-            _chk(lib.vp_bn_relu_bwd_f32(hctx, dy.data_ptr(), Cout, z.data_ptr(), Cout, mu.data_ptr(), istd.data_ptr(),
-                                        g.data_ptr() if g is not None else None, sums.data_ptr(), M, Cout, int(relu),
-                                        dz.data_ptr(), Cout, N.stream_ptr()), hctx)
-            dbias = col_sums(dz)[0] if has_bias else None
+        # the bias gradient (column sums of dz) from the pass that writes dz where that pass can be four channels wide
+        dz, dbias = _bn_bwd_dz(dy, z, mu, istd, g, sums, relu_mask=relu, want_dbias=has_bias and Cout % 4 == 0, bf16_out=bool(wide), utt=utt)
+        if has_bias and dbias is None:
+            dbias = col_sums(dz)[0]
     else:
         dz = dy
         if has_bias and getattr(ctx, 'given_dbias', None) is not None:      # the caller's own pass over dz already summed its columns
@@ -1269,13 +1325,12 @@ class BNRows(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, gamma, beta, run_mean, run_var, momentum, eps, relu=False):
-        lib, hctx = N.lib(), N.ctx(x.device)
         x = _f32c(x)
         M, Cc = x.shape
         if Cc % 4:
             raise N.VpmiError(f'BNRows: C = {Cc} is no multiple of 4 (the apply and backward passes are four channels wide)')
         d, negc, mean, invstd, scale, shift = bn_centred_stats(x, Cc, M, Cc, gamma, beta, run_mean, run_var, momentum, eps)
-        y = _affine_rows(d, Cc, M, Cc, scale, shift, torch.empty_like(x), int(relu))
+        y = _affine_rows(d, Cc, M, Cc, scale, shift, relu=int(relu))
         fold = bool(relu) and not os.environ.get('VPMI_BN_RELU_UNFOLDED')
         ctx.fold = (scale, shift) if fold else None
         ctx.neg_center = negc                                  # the batch mean of x is the saved mean (of d) - neg_center
@@ -1285,34 +1340,11 @@ class BNRows(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, mean, invstd, gamma, yr = ctx.saved_tensors
-        lib, hctx = N.lib(), N.ctx(x.device)
         dy = _f32c(dy)
-        M, Cc = x.shape
-        fold = ctx.fold
-        if fold is not None:
-            ms, mh = fold
-            sums = torch.empty((2, Cc), dtype=torch.float32, device=x.device)
-            ws = _bytes(lib.vp_col_sums_workspace_bytes(M, Cc), x.device)
-            rc = lib.vp_col_sums_masked_f32(hctx, dy.data_ptr(), Cc, x.data_ptr(), Cc, mean.data_ptr(), invstd.data_ptr(), ms.data_ptr(),
-                                            mh.data_ptr(), 0.0, M, Cc, sums.data_ptr(), ws.data_ptr(), ws.numel(), N.stream_ptr())
-            if rc == N.VP_EUNSUP:                     # (misaligned views: materialise the mask the plain way)
-                yr = torch.empty_like(x)
-                _chk(lib.vp_affine_rows_f32(hctx, x.data_ptr(), Cc, ms.data_ptr(), mh.data_ptr(), M, Cc, yr.data_ptr(), Cc, 1, N.stream_ptr()), hctx)
-                fold = None
-            else:
-                _chk(rc, hctx)
-                dx = torch.empty_like(x)
-                _chk(lib.vp_bn_relu_bwd_masked_f32(hctx, dy.data_ptr(), Cc, x.data_ptr(), Cc, mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(),
-                                                   sums.data_ptr(), ms.data_ptr(), mh.data_ptr(), 0.0, M, Cc, dx.data_ptr(), Cc, 0, N.stream_ptr()), hctx)
-                return dx, sums[1], sums[0], None, None, None, None, None
-        if yr is not None:
-            t = torch.empty_like(dy)
-            _chk(lib.vp_act_bwd_f32(hctx, N.VP_ACT_RELU, dy.data_ptr(), yr.data_ptr(), dy.numel(), t.data_ptr(), N.stream_ptr()), hctx)
-            dy = t
-        sums = col_sums(dy, x, mean, invstd)
-        dx = torch.empty_like(x)
-        _chk(lib.vp_bn_relu_bwd_f32(hctx, dy.data_ptr(), Cc, x.data_ptr(), Cc, mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(),
-                                    sums.data_ptr(), M, Cc, 0, dx.data_ptr(), Cc, N.stream_ptr()), hctx)
+        if ctx.fold is not None:
+            dx, sums = _bn_act_bwd(dy, x, mean, invstd, gamma, (*ctx.fold, 0.0))
+        else:
+            dx, sums = _bn_bwd(dy if yr is None else _act_bwd(N.VP_ACT_RELU, dy, yr), x, mean, invstd, gamma)
         return dx, sums[1], sums[0], None, None, None, None, None
 
 
@@ -1537,21 +1569,14 @@ class Conv2dBlock(torch.autograd.Function):
         y = z
         clamp = 0
         if bn:
-            zeros, ones = _const(0.0, Cout, x.device), _const(1.0, Cout, x.device)
-            sums = col_sums(z, z, zeros, ones)
-            mean, invstd, scale, shift = (torch.empty(Cout, dtype=torch.float32, device=x.device) for _ in range(4))
-            _chk(lib.vp_bn_train_finalize(hctx, sums[0].data_ptr(), sums[1].data_ptr(), 1, z.shape[0], Cout, gamma.data_ptr(),
-                                          beta.data_ptr(), run_mean.data_ptr() if run_mean is not None else None,
-                                          run_var.data_ptr() if run_var is not None else None, cfg.get('momentum', 0.9),
-                                          cfg.get('eps', 1e-5), mean.data_ptr(), invstd.data_ptr(), scale.data_ptr(),
-                                          shift.data_ptr(), N.stream_ptr()), hctx)
+            sums = _raw_sums(z)
+            mean, invstd, scale, shift = _bn_finalize(sums[0], sums[1], 1, z.shape[0], Cout, gamma, beta, run_mean, run_var,
+                                                      cfg.get('momentum', 0.9), cfg.get('eps', 1e-5))
             # ReLU and Hardtanh(0, 20) (ERes2Net's "ReLU", eres2net.py:14-22) leave with the apply pass; the other activations get their own
             clamp = {N.VP_ACT_RELU: 1, N.VP_ACT_HARDTANH20: 2}.get(act, 0)
             if clamp == 2 and os.environ.get('VPMI_BN_RELU_UNFOLDED'):
                 clamp = 0
-            y = torch.empty_like(z)
-            _chk(lib.vp_affine_rows_f32(hctx, z.data_ptr(), Cout, scale.data_ptr(), shift.data_ptr(), z.shape[0], Cout, y.data_ptr(),
-                                        Cout, clamp, N.stream_ptr()), hctx)
+            y = _affine_rows(z, Cout, z.shape[0], Cout, scale, shift, relu=clamp)
         pre = y                                       # the activation's input (SiLU's backward needs it)
         if act and not (bn and clamp):
             y = torch.empty_like(pre)
@@ -1571,45 +1596,21 @@ class Conv2dBlock(torch.autograd.Function):
         lib, hctx = N.lib(), N.ctx(x.device)
         dev = x.device
         dy = _f32c(dy)
-        M = B * To * Fo
-        fold = getattr(ctx, 'fold', None)
-        if fold is not None:                          # BatchNorm -> ReLU with the mask folded into the two passes below
-            ms, mh, hi = fold
-            sums = torch.empty((2, Cout), dtype=torch.float32, device=dev)
-            ws = _bytes(lib.vp_col_sums_workspace_bytes(M, Cout), dev)
-            rc = lib.vp_col_sums_masked_f32(hctx, dy.data_ptr(), Cout, z.data_ptr(), Cout, mean.data_ptr(), invstd.data_ptr(), ms.data_ptr(),
-                                            mh.data_ptr(), hi, M, Cout, sums.data_ptr(), ws.data_ptr(), ws.numel(), N.stream_ptr())
-            if rc == N.VP_EUNSUP:                     # (misaligned views: materialise the mask the plain way)
-                yr = torch.empty_like(z)
-                _chk(lib.vp_affine_rows_f32(hctx, z.data_ptr(), Cout, ms.data_ptr(), mh.data_ptr(), M, Cout, yr.data_ptr(), Cout,
-                                            2 if hi else 1, N.stream_ptr()), hctx)
-                fold = None
-            else:
-                _chk(rc, hctx)
-        if fold is not None:
-            dgamma, dbeta = sums[1], sums[0]
-            dz = torch.empty_like(dy)
-            _chk(lib.vp_bn_relu_bwd_masked_f32(hctx, dy.data_ptr(), Cout, z.data_ptr(), Cout, mean.data_ptr(), invstd.data_ptr(),
-                                               gamma.data_ptr(), sums.data_ptr(), ms.data_ptr(), mh.data_ptr(), hi, M, Cout, dz.data_ptr(), Cout,
-                                               0, N.stream_ptr()), hctx)
-            bn = False                                # (done)
-        elif relu:                                    # `relu` holds the activation code here
-            t = torch.empty_like(dy)
-            _chk(lib.vp_act_bwd_f32(hctx, relu, dy.data_ptr(), yr.data_ptr(), dy.numel(), t.data_ptr(), N.stream_ptr()), hctx)
-            dy = t
-        if fold is None:
-            dgamma = dbeta = None
-            dz = dy
+        dgamma = dbeta = None
+        dz = dy
+        if getattr(ctx, 'fold', None) is not None:    # BatchNorm -> ReLU / Hardtanh with the mask folded into the two backward passes
+            dz, sums = _bn_act_bwd(dy, z, mean, invstd, gamma, ctx.fold)
+        else:
+            if relu:                                  # `relu` holds the activation code here
+                dz = _act_bwd(relu, dy, yr)
+            if bn:
+                dz, sums = _bn_bwd(dz, z, mean, invstd, gamma)
         if bn:
-            sums = col_sums(dy, z, mean, invstd)
             dgamma, dbeta = sums[1], sums[0]
-            dz = torch.empty_like(dy)
-            _chk(lib.vp_bn_relu_bwd_f32(hctx, dy.data_ptr(), Cout, z.data_ptr(), Cout, mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(),
-                                        sums.data_ptr(), M, Cout, 0, dz.data_ptr(), Cout, N.stream_ptr()), hctx)
         # a conv bias directly in front of a train-mode BatchNorm: sum_rows dz is IDENTICALLY zero (dz = gamma invstd (dy - mean(dy) - zhat
         # mean(dy zhat)), sum zhat = 0) -- what a column-sum pass returns there is rounding noise (1e-9 of the gradient scale, in the
         # reference's autograd as here); the pass is not launched.  VPMI_BN_BIAS_GRAD_SUMS=1 runs it.
-        if has_bias and ctx.geom[12] and not os.environ.get('VPMI_BN_BIAS_GRAD_SUMS'):
+        if has_bias and bn and not os.environ.get('VPMI_BN_BIAS_GRAD_SUMS'):
             dbias = torch.zeros(Cout, dtype=torch.float32, device=dev)
         else:
             dbias = col_sums(dz)[0] if has_bias else None
@@ -1854,7 +1855,7 @@ class CamDenseBlockFn(torch.autograd.Function):
             # nonlinear1: BatchNorm (batch statistics) -> ReLU over the first Cl columns, read where they are
             # (the same centred statistics as BNRows, which the per-layer form of this block runs here; d is formed again in backward)
             d, negc, mean, invstd, scale, shift = bn_centred_stats(X, Cf, M, Cl, g1, be1, rm1, rv1, mom1, eps1)
-            h0 = _affine_rows(d, Cl, M, Cl, scale, shift, torch.empty((M, Cl), dtype=torch.float32, device=dev), 1)
+            h0 = _affine_rows(d, Cl, M, Cl, scale, shift, relu=1)
             del d
             t2, t3, t4 = _Tape((True,) * 9), _Tape((True,) * 8), _Tape((True,) * 8)
             # (linear1's bias sits directly in front of nonlinear2's BatchNorm: its gradient is identically zero, see Conv2dBlock.backward)
@@ -1872,7 +1873,6 @@ class CamDenseBlockFn(torch.autograd.Function):
     def backward(ctx, g):
         (X,) = ctx.saved_tensors
         M, C0, G, L, Cf = ctx.geom
-        lib, hctx = N.lib(), N.ctx(X.device)
         dev = X.device
         # ONE gradient buffer for the whole block, updated in place.  A copy of the incoming gradient (one pass per block): autograd's
         # tensors are not ours to write into (a retain_grad() or a hook on the block output would see the sums)
@@ -1886,14 +1886,8 @@ class CamDenseBlockFn(torch.autograd.Function):
             r3 = BNRows.backward(t3, r4[0])
             r2 = _conv_block_bwd(t2, r3[0])
             dh0 = r2[0]
-            sums = torch.empty((2, Cl), dtype=torch.float32, device=dev)
-            ws = _bytes(lib.vp_col_sums_workspace_bytes(M, Cl), dev)
-            d = _affine_rows(X, Cf, M, Cl, _const(1.0, Cl, dev), negc, torch.empty((M, Cl), dtype=torch.float32, device=dev))
-            _chk(lib.vp_col_sums_masked_f32(hctx, dh0.data_ptr(), Cl, d.data_ptr(), Cl, mean.data_ptr(), invstd.data_ptr(), scale.data_ptr(),
-                                            shift.data_ptr(), 0.0, M, Cl, sums.data_ptr(), ws.data_ptr(), ws.numel(), N.stream_ptr()), hctx)
-            _chk(lib.vp_bn_relu_bwd_masked_f32(hctx, dh0.data_ptr(), Cl, d.data_ptr(), Cl, mean.data_ptr(), invstd.data_ptr(), g1.data_ptr(),
-                                               sums.data_ptr(), scale.data_ptr(), shift.data_ptr(), 0.0, M, Cl, Gb.data_ptr(), Cf, 1,
-                                               N.stream_ptr()), hctx)
+            d = _affine_rows(X, Cf, M, Cl, _const(1.0, Cl, dev), negc)
+            _, sums = _bn_act_bwd(dh0, d, mean, invstd, g1, (scale, shift, 0.0), dst=Gb, accumulate=True)
             grads[12 * l:12 * l + 12] = [sums[1], sums[0], r2[1], r2[2], r3[1], r3[2], r4[1], r4[2], r4[3], r4[4], r4[5], r4[6]]
         return (Gb[:, :C0].contiguous(), None, *grads)
 
