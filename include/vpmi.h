@@ -1047,6 +1047,32 @@ int vp_eigs_init_f32(vp_ctx* ctx, const float* L, int N, int k, void* ws, size_t
 int vp_eigs_iterate_f32(vp_ctx* ctx, const float* L, int N, int k, int steps, void* ws, size_t ws_bytes, float* evals, float* evecs,
                         float* resid, float* bounds, vp_stream stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * 1:N speaker search over a gallery that stays on the device (csrc/gallery.hip, docs/gallery.md) -- PPVectorPredictor's voice-print
+ * library (predict.py:154-187).  f32 throughout: this is a selection, a narrower format would change which rows win.
+ * vp_gallery_centroids_f32 -- replaces the per-user mean of predict.py:154-164 (audio_feature_mean): group g = rows offsets[g] ..
+ *   offsets[g+1]-1 of emb (M, D), added in ascending row order, divided by the count, scaled to unit length, written to row
+ *   dst_rows[g] of centroids (row stride D).  A group whose mean has zero length (or no rows) writes a zero row.  emb, offsets (n+1)
+ *   and dst_rows (n) are device arrays; the dst_rows are distinct.  One workgroup per group, no atomics: a full rebuild (all users, emb
+ *   sorted by user) and an incremental update (n = 1, emb = that user's rows) give the same bits.
+ * vp_gallery_topk_f32 -- replaces the retrieval of predict.py:173-187 (cosine_similarity over the whole library + argmax): for each
+ *   of the Q raw queries (Q, D) -- normalised inside, a zero query scores 0 against everything -- the k best rows of centroids (U, D)
+ *   (unit rows as vp_gallery_centroids_f32 writes them; the score is the plain dot product with the unit query), ordered by score
+ *   descending, then row ascending: a tie goes to the lower row, k = 1 is np.argmax.  out_idx (Q, k) int32, out_score (Q, k) f32;
+ *   U < k: the tail of a row is idx = -1, score = -inf.  The (Q, U) scores are never written to global memory: workgroups of the
+ *   first kernel walk slabs of VP_GALLERY_SLAB rows and leave one k-entry list per (query, workgroup) in the workspace, a second
+ *   kernel merges them (one workgroup per query).  A score is one k-ordered fma chain over D on the exact-f32 matrix cores and does
+ *   not depend on U, the slab or the grid; no float atomics, no grid barrier: two runs give the same bits.
+ *   Q, U >= 1, D % 4 == 0, D <= 1024, 1 <= k <= 32, U D < 2^31 and 16-byte aligned rows; anything else: the workspace query returns
+ *   0 and the entry point VP_EUNSUP (checked before anything touches a device).  Workspace too small: VP_EWORKSPACE.
+ * ---------------------------------------------------------------------------------------------- */
+#define VP_GALLERY_SLAB 128
+int vp_gallery_centroids_f32(vp_ctx* ctx, const float* emb, const int* offsets, const int* dst_rows, int n, int D, float* centroids,
+                             vp_stream stream);
+size_t vp_gallery_topk_workspace_bytes(int Q, int U, int D, int k);
+int vp_gallery_topk_f32(vp_ctx* ctx, const float* queries, int Q, const float* centroids, int U, int D, int k, int* out_idx,
+                        float* out_score, void* ws, size_t ws_bytes, vp_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,9 @@ mask, one featurizer call, backbone in chunks), ``contrast`` (:271-283) and the 
 (:173-187, :337-342) -- Fbank+CMN, backbone forward and cosine scoring all go through libvpmi.
 Host bookkeeping kept in Python as in the reference: audio decoding / resampling / dB normalisation
 (``_load_audio`` :189-216, yeaudio semantics restated for PCM WAV + ndarray input), the user index
-(pickle ``audio_indexes.bin`` with the reference's key names, :86-109).
+(pickle ``audio_indexes.bin`` with the reference's key names, :86-109).  The per-user means the search runs over (:154-164) are kept
+as unit centroids in a device matrix (``ppvector/infer_utils/gallery.py``, docs/gallery.md) in step with the index: a query
+computes and uploads nothing but its own embedding.
 ``speaker_diarization`` (:366-396): the windows are cut, padded and normalised on the GPU from one upload of the recording, embedded
 by the same featurizer + backbone, and clustered through the pruned-affinity and Laplacian kernels (``ppvector/infer_utils``); the
 voice-activity detection in front of it is not built -- the caller passes the speech regions.
@@ -23,6 +25,7 @@ import yaml
 from torch import nn
 
 from ppvector.data_utils.featurizer import AudioFeaturizer
+from ppvector.infer_utils.gallery import SpeakerGallery
 from ppvector.infer_utils.speaker_diarization import SpeakerDiarization, chunk_batch
 from ppvector.metric.metrics import cosine_score_matrix
 from ppvector.models import build_model
@@ -119,6 +122,7 @@ class PPVectorPredictor:
         self.predictor.to(self.device).eval()
         self.audio_feature = None
         self.users_name, self.users_audio_path = [], []
+        self.gallery = None                                    # SpeakerGallery, made with the first enrolled embedding's width
         self.audio_db_path = audio_db_path
         self.speaker_diarize = SpeakerDiarization()
         if self.audio_db_path is not None:
@@ -137,6 +141,23 @@ class PPVectorPredictor:
             self.users_name.append(name)
             self.users_audio_path.append(path)
             self.audio_feature = feature[None] if self.audio_feature is None else np.vstack((self.audio_feature, feature))
+        if self.audio_feature is not None:
+            self.__gallery().rebuild(self.users_name, self.audio_feature)
+
+    def __gallery(self):
+        if self.gallery is None:
+            self.gallery = SpeakerGallery(self.audio_feature.shape[1], self.device)
+        return self.gallery
+
+    def __gallery_set(self, user_name):
+        """One user's row of the gallery from that user's rows of ``audio_feature``."""
+        rows = [i for i, n in enumerate(self.users_name) if n == user_name]
+        self.__gallery().set_user(user_name, self.audio_feature[rows])
+
+    def __search(self, features, top_k=1):
+        """(Q, D) embeddings -> host (idx, score) arrays (Q, top_k) of the best enrolled users (``self.gallery.names[idx]``)."""
+        idx, score = self.gallery.search(torch.from_numpy(np.ascontiguousarray(features, dtype=np.float32)).to(self.device), top_k)
+        return idx.cpu().numpy(), score.cpu().numpy()
 
     def __write_index(self):
         with open(self.audio_indexes_path, "wb") as f:
@@ -160,6 +181,8 @@ class PPVectorPredictor:
             self.users_name.append(name)
             self.users_audio_path.append(p)
             self.audio_feature = feat[None] if self.audio_feature is None else np.vstack((self.audio_feature, feat))
+        for name in dict.fromkeys(n for n, _ in todo):
+            self.__gallery_set(name)
         if todo:
             self.__write_index()
 
@@ -235,6 +258,7 @@ class PPVectorPredictor:
         self.users_name.append(user_name)
         self.users_audio_path.append(path)
         self.audio_feature = feat[None] if self.audio_feature is None else np.vstack((self.audio_feature, feat))
+        self.__gallery_set(user_name)
         if self.audio_db_path is not None:
             self.__write_index()
         return True, "注册成功"
@@ -246,14 +270,24 @@ class PPVectorPredictor:
         if self.audio_feature is None:
             return None, None
         feat = self.predict(audio_data, sample_rate=sample_rate)
-        users = sorted(set(self.users_name))
-        means = np.stack([self.audio_feature[[i for i, n in enumerate(self.users_name) if n == u]].mean(axis=0) for u in users])
-        s = cosine_score_matrix(torch.from_numpy(feat[None]).to(self.device),
-                                torch.from_numpy(means.astype(np.float32)).to(self.device)).cpu().numpy()[0]
-        i = int(np.argmax(s))
-        if s[i] >= self.threshold:
-            return users[i], round(float(s[i]), 5)
+        idx, score = self.__search(feat[None])
+        i, s = int(idx[0, 0]), float(score[0, 0])
+        if i >= 0 and s >= self.threshold:
+            return self.gallery.names[i], round(s, 5)
         return None, None
+
+    def recognition_batch(self, audios_data, threshold=None, sample_rate=16000, batch_size=32, top_k=1):
+        """声纹识别 of a batch: one list per utterance of up to ``top_k`` (name, score) pairs at or above the threshold, best first
+        (empty when nothing passes).  The embeddings are ``predict_batch``'s, as the reference's ``__retrieval`` takes a batch."""
+        if threshold:
+            self.threshold = threshold
+        if self.audio_feature is None:
+            return [[] for _ in audios_data]
+        feats = self.predict_batch(audios_data, sample_rate=sample_rate, batch_size=batch_size)
+        idx, score = self.__search(feats, top_k)
+        names = self.gallery.names
+        return [[(names[i], round(float(s), 5)) for i, s in zip(ri, rs) if i >= 0 and s >= self.threshold]
+                for ri, rs in zip(idx, score)]
 
     def get_users(self):
         return self.users_name
@@ -290,12 +324,9 @@ class PPVectorPredictor:
         outputs = self.speaker_diarize.postprocess(table, labels)
         if search_audio_db:
             assert self.audio_feature is not None, "数据库中没有音频数据，请先指定说话人特征数据库或者注册说话人"
-            users = sorted(set(self.users_name))
-            means = np.stack([self.audio_feature[[i for i, n in enumerate(self.users_name) if n == u]].mean(axis=0) for u in users])
-            s = cosine_score_matrix(torch.from_numpy(spk_center_embeddings.astype(np.float32)).to(self.device),
-                                    torch.from_numpy(means.astype(np.float32)).to(self.device)).cpu().numpy()
-            best = np.argmax(s, axis=1)
-            names = [users[j] if s[i, j] >= self.threshold else None for i, j in enumerate(best)]
+            idx, score = self.__search(spk_center_embeddings)
+            users = self.gallery.names
+            names = [users[j] if j >= 0 and s >= self.threshold else None for j, s in zip(idx[:, 0], score[:, 0])]
             outputs = [dict(speaker=names[o['speaker']] if names[o['speaker']] else f"陌生人{o['speaker']}",
                             start=o['start'], end=o['end']) for o in outputs]
         return outputs
@@ -309,6 +340,7 @@ class PPVectorPredictor:
         self.users_name = [self.users_name[i] for i in keep]
         self.users_audio_path = [self.users_audio_path[i] for i in keep]
         self.audio_feature = self.audio_feature[keep] if keep else None
+        self.gallery.remove(user_name)
         if self.audio_db_path is not None:
             self.__write_index()
         return True
