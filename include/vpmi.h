@@ -1073,6 +1073,43 @@ size_t vp_gallery_topk_workspace_bytes(int Q, int U, int D, int k);
 int vp_gallery_topk_f32(vp_ctx* ctx, const float* queries, int Q, const float* centroids, int U, int D, int k, int* out_idx,
                         float* out_score, void* ws, size_t ws_bytes, vp_stream stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * EER / minDCF without the (Nt, Ne) score matrix (csrc/trial_ranks.hip, docs/trial_ranks.md) -- the scoring of
+ * PPVectorTrainer.evaluate.  What the fnr / fpr arithmetic needs is the NT target scores (pairs with equal labels), sorted, and for
+ * every gap between two of them the NUMBER of non-target scores in it; nothing of size Nt Ne is written anywhere.  f32 throughout on
+ * the exact-f32 matrix cores: this is a ranking, a narrower format would move pairs across targets.  A score is the dot product of
+ * the two unit rows (lengths in float64, a zero row scores 0), one k-ordered fma chain that does not depend on the tile, the wave,
+ * the grid or the row's position: bit-identical rows give bit-identical scores, in every pass.  Integer counts only: no float
+ * atomics, no grid barrier, no spinning; two runs give the same bits.  Labels are int32 device arrays.
+ * Nt, Ne >= 1, D % 4 == 0, D <= 1024, 16-byte aligned rows, 1 <= NT <= 2^24; anything else: the workspace query returns 0 and the
+ * entry points VP_EUNSUP (checked before anything touches a device).  Workspace too small: VP_EWORKSPACE.  The workspace,
+ * (Nt + Ne) D floats, carries the unit rows from vp_trial_ranks_targets_f32 to the later passes of the same lists.
+ * vp_trial_ranks_targets_f32 -- replaces the per-trial cosine loop of trainer.py:416-423 for the pairs labelled 1: writes the unit
+ *   rows of trials (Nt, D) and enroll (Ne, D) into the workspace, then the score of every pair (i, j) with trial_labels[i] ==
+ *   enroll_labels[j] to targets[trial_offsets[i] + enroll_ranks[j]] -- enroll_ranks[j] = the rank of row j among the enrol rows of
+ *   its label, trial_offsets[i] = the number of targets of the trials before i (both follow from the labels alone; NT = their total):
+ *   the place does not depend on arrival order.  The caller sorts targets ascending.
+ * vp_trial_ranks_counts_f32 -- replaces np.argsort over all scores and the two cumulative sums of metric/metrics.py:4-17
+ *   (compute_fnr_fpr): hist (NT + 1) int64, zeroed here, hist[b] = the number of non-target pairs whose score s has
+ *   b = #{j : sorted_targets[j] < s} (a non-target equal to a target sorts before it).  The bin is found by binary search, in LDS
+ *   when 2 NT + 1 words fit beside the tile, else in up to 2048 LDS pivots and then between two pivots in global memory; counts are
+ *   kept per workgroup in LDS (the lowest bins, as many as fit) and added to hist once per workgroup and non-zero bin.
+ * vp_trial_ranks_select_f32 -- replaces np.sort(scores)[hi] of metric/metrics.py:20-29 (compute_eer's threshold) when position hi is
+ *   a non-target: one digit of a radix selection among the non-target scores with lo < s <= hi.  key(s) = the bits of s, all flipped
+ *   when negative, else the sign bit set (orders as s does).  level 0, 1, 2 counts into digits (2048 int64, zeroed here) bits 31-21,
+ *   20-10, 9-0 of the keys that agree with prefix in the bits above the digit.  Memory does not depend on how many scores qualify.
+ * ---------------------------------------------------------------------------------------------- */
+size_t vp_trial_ranks_workspace_bytes(int Nt, int Ne, int D, long long NT);
+int vp_trial_ranks_targets_f32(vp_ctx* ctx, const float* trials, const int* trial_labels, const long long* trial_offsets, int Nt,
+                               const float* enroll, const int* enroll_labels, const int* enroll_ranks, int Ne, int D, long long NT,
+                               float* targets, void* ws, size_t ws_bytes, vp_stream stream);
+int vp_trial_ranks_counts_f32(vp_ctx* ctx, const int* trial_labels, int Nt, const int* enroll_labels, int Ne, int D,
+                              const float* sorted_targets, long long NT, long long* hist, const void* ws, size_t ws_bytes,
+                              vp_stream stream);
+int vp_trial_ranks_select_f32(vp_ctx* ctx, const int* trial_labels, int Nt, const int* enroll_labels, int Ne, int D, long long NT,
+                              float lo, float hi, int level, long long prefix, long long* digits, const void* ws, size_t ws_bytes,
+                              vp_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

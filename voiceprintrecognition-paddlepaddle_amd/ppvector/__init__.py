@@ -107,6 +107,25 @@ def get_spectral_solver():
     return _SPECTRAL_SOLVER
 
 
+_TRIAL_SCORER = 'matrix'
+
+
+def set_trial_scorer(name):
+    """How ``ppvector.metric.metrics.evaluate_trials`` (the scoring of PPVectorTrainer.evaluate) gets from embeddings to EER / minDCF:
+    'matrix'  the (Nt, Ne) cosine matrix on the GPU, then the reference's argsort / cumulative sums over all pairs on the host --
+              the default;
+    'fused'   the sorted target scores and the number of non-target scores between them, counted on the GPU without the matrix
+              (csrc/trial_ranks.hip, docs/trial_ranks.md): memory O((Nt + Ne) D + targets), the same float64 rate arithmetic."""
+    global _TRIAL_SCORER
+    if name not in ('matrix', 'fused'):
+        raise ValueError(f'unsupported trial scorer {name}')
+    _TRIAL_SCORER = name
+
+
+def get_trial_scorer():
+    return _TRIAL_SCORER
+
+
 _FUSED_GRID_KERNELS = True
 
 
