@@ -113,6 +113,12 @@ __device__ __forceinline__ float vp_wave_max(float v) {
     return v;
 }
 
+// a float's bits as an unsigned that orders as the float does (ppvector/metric/metrics.py: kth_nontarget inverts it)
+__device__ __forceinline__ unsigned vp_order_key(float s) {
+    const unsigned u = __float_as_uint(s);
+    return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
+}
+
 static inline size_t vp_dtype_size(int dt) { return dt == VP_BF16 ? 2 : 4; }
 // a backbone's `dtype` -> the element type of its tensors (VP_F32X3 = f32 tensors, split-precision contractions)
 static inline int vp_storage_dtype(int dt) { return dt == VP_F32X3 ? VP_F32 : dt; }

@@ -81,11 +81,6 @@ __global__ __launch_bounds__(256) void affinity_prep_kernel(const float* __restr
     }
 }
 
-__device__ __forceinline__ unsigned ordered_key(float v) {          // unsigned order == float order
-    const unsigned u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 // One workgroup per block of R rows.  Dynamic LDS: sims[R][N] | xs[R][Dp] (the block's own normalised rows, Dp = D rounded up to 4).
 // Thread t owns columns t, t + 256, ... in every phase after the products, so the phases of one row need no barrier between them
 // beyond the ones of the selection itself.
@@ -152,7 +147,7 @@ __global__ __launch_bounds__(256) void affinity_prune_kernel(const float* __rest
                 hist[tid] = 0;
                 __syncthreads();
                 for (int j = tid; j < N; j += 256) {
-                    const unsigned key = ordered_key(srow[j]);
+                    const unsigned key = vp_order_key(srow[j]);
                     if (pass == 0 || ((key ^ prefix) >> (shift + 8)) == 0) atomicAdd(&hist[(key >> shift) & 255u], 1u);
                 }
                 __syncthreads();
@@ -177,7 +172,7 @@ __global__ __launch_bounds__(256) void affinity_prune_kernel(const float* __rest
                 unsigned running = 0;
                 for (int jb = 0; jb < N && running < kth; jb += 256) {
                     const int j = jb + tid;
-                    const bool tie = j < N && ordered_key(srow[j]) == prefix;
+                    const bool tie = j < N && vp_order_key(srow[j]) == prefix;
                     const unsigned long long m = __ballot(tie);
                     if (lane == 0) wtot[w] = (unsigned)__popcll(m);
                     __syncthreads();
@@ -188,10 +183,10 @@ __global__ __launch_bounds__(256) void affinity_prune_kernel(const float* __rest
                     __syncthreads();
                 }
                 for (int j = tid; j < N; j += 256)
-                    if (ordered_key(srow[j]) < prefix) srow[j] = 0.f;
+                    if (vp_order_key(srow[j]) < prefix) srow[j] = 0.f;
             } else {
                 for (int j = tid; j < N; j += 256)
-                    if (ordered_key(srow[j]) <= prefix) srow[j] = 0.f;
+                    if (vp_order_key(srow[j]) <= prefix) srow[j] = 0.f;
             }
         }
         float* prow = P + (size_t)i * N;

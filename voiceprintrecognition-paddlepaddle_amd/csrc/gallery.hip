@@ -3,36 +3,26 @@
 //
 // vp_gallery_centroids_f32   one workgroup per user: the user's rows added in ascending row order (a thread per column), divided by the
 //                            count, scaled to unit length.  The same kernel rebuilds every row or one.
-// vp_gallery_topk_f32        gallery_score_kernel: a workgroup holds a tile of 32 normalised queries in LDS ([k][query], the B operand
-//                            of v_mfma_f32_32x32x2_f32) and walks `slabs_per_wg` slabs of VP_GALLERY_SLAB = 128 centroid rows; each of
-//                            its four waves owns 32 rows of a slab, reads them as 16-byte loads (lane (c, half) takes floats
-//                            8g + 4 half .. + 3 of row c; a v_permlane32_swap pair puts k, k + 1 on the two halves) and keeps the
-//                            32 x 32 scores in one accumulator over ALL of D.  A score is therefore one k-ordered fma chain
-//                            (ascending k, the matrix core's own order inside a pair) whatever U, the slab, the wave or the grid:
+// vp_gallery_topk_f32        gallery_score_kernel: a workgroup normalises a tile of 32 queries into LDS and walks `slabs_per_wg` slabs
+//                            of VP_GALLERY_SLAB centroid rows with cos_tile.h's walk, which states how a score is summed and why
 //                            bit-identical rows get bit-identical scores.  Per wave and query a list of k (score, row) lives in LDS,
 //                            unordered but for its worst entry at k - 1 (while places are empty: an empty one that counts the taken
 //                            ones); a lane replaces that entry only when its score beats it.
 //                            At the end eight lanes per query rank the entries of the four lists and write the best k as ONE
 //                            sorted partial list per (query, workgroup).
-//                            (The two normalisations take their lengths in float64, so a unit vector is rounded once per element.)
 //                            gallery_merge_kernel: a workgroup per query copies its partial lists to LDS and merges them (k rounds of a
 //                            block-wide best-head selection over sorted lists).
 // Order everywhere: score descending, then row ascending.  No atomics, no grid barrier, fixed order of every sum: two runs give the
 // same bits.  f32 throughout: a narrower gallery would change which rows win (the rule of diarize.hip's selection).
-#include "common.h"
-
-#include <math.h>
+#include "cos_tile.h"
 
 namespace {
 
-constexpr int SLAB = VP_GALLERY_SLAB;   // 4 waves x 32 rows
-constexpr int QT = 32;                  // queries of a tile = the matrix core's N
-constexpr int MAX_K = 32, MAX_D = 1024;
+using cos_tile::SLAB;
+using cos_tile::MAX_D;
+constexpr int QT = cos_tile::COLS;      // queries of a tile
+constexpr int MAX_K = 32;
 constexpr int MAX_RANGES = 512;         // partial lists per query: 2 per thread of the merge kernel, 512 x 32 x 8 B = 128 KB of its LDS
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
-static_assert(SLAB == 128, "the score kernel's four waves take 32 rows each");
 
 struct Plan {
     int slabs_per_wg, ranges, qtiles;
@@ -90,21 +80,6 @@ __global__ __launch_bounds__(256) void gallery_centroid_kernel(const float* __re
 }
 
 // ------------------------------------------------------------------------------------------------ scores and per-workgroup lists
-// Eight consecutive k of the wave's 32 rows x the tile's 32 queries.  In: lane (c, half) holds k0 + 4 half + {0, 1, 2, 3} of its row in
-// v; the two swaps leave (k0, k0 + 1), (k0 + 2, k0 + 3), (k0 + 4, k0 + 5), (k0 + 6, k0 + 7) on (lower half, upper half) of x, z, y, w.
-// FULL = false: the last four k of a D that is no multiple of 8 -- the upper half's v is zero and only x, z are used.
-template <bool FULL>
-__device__ __forceinline__ void mma_group(float4 v, const float* __restrict__ qb, int c, int half, f32x16& acc) {
-    const auto xy = __builtin_amdgcn_permlane32_swap(__float_as_uint(v.x), __float_as_uint(v.y), false, false);
-    const auto zw = __builtin_amdgcn_permlane32_swap(__float_as_uint(v.z), __float_as_uint(v.w), false, false);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(xy[0]), qb[(0 + half) * QT + c], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(zw[0]), qb[(2 + half) * QT + c], acc, 0, 0, 0);
-    if (FULL) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(xy[1]), qb[(4 + half) * QT + c], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(zw[1]), qb[(6 + half) * QT + c], acc, 0, 0, 0);
-    }
-}
-
 // grid (query tiles, row ranges), 256 threads, dynamic LDS: qs [Dp][32] | list scores [4][32][kp] | list rows [4][32][kp]
 __global__ __launch_bounds__(256) void gallery_score_kernel(const float* __restrict__ queries, int Q, const float* __restrict__ G, int U,
                                                             int D, int k, int slabs_per_wg, int ranges, float* __restrict__ part_s,
@@ -118,64 +93,14 @@ __global__ __launch_bounds__(256) void gallery_score_kernel(const float* __restr
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 31, half = lane >> 5;
     const int qt = blockIdx.x, range = blockIdx.y;
 
-    {   // the query tile, normalised: eight threads per query, 16-byte loads; queries past Q and the k past D are zero
-        const int j = tid >> 3, sub = tid & 7;
-        const int q = qt * QT + j;
-        const bool qv = q < Q;
-        const float* src = queries + (size_t)(qv ? q : 0) * D;
-        double ss = 0.0;                        // the length in float64 (32 x D elements per workgroup): one rounding per element
-        for (int kk = sub * 4; kk < D; kk += 32) {
-            const float4 v = *reinterpret_cast<const float4*>(src + kk);
-            ss += (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
-        }
-        ss += __shfl_xor(ss, 1);
-        ss += __shfl_xor(ss, 2);
-        ss += __shfl_xor(ss, 4);
-        const double inv = (qv && ss > 0.0) ? 1.0 / sqrt(ss) : 0.0;
-        for (int kk = sub * 4; kk < D; kk += 32) {
-            const float4 v = *reinterpret_cast<const float4*>(src + kk);
-            qs[(kk + 0) * QT + j] = qv ? (float)(v.x * inv) : 0.f;
-            qs[(kk + 1) * QT + j] = qv ? (float)(v.y * inv) : 0.f;
-            qs[(kk + 2) * QT + j] = qv ? (float)(v.z * inv) : 0.f;
-            qs[(kk + 3) * QT + j] = qv ? (float)(v.w * inv) : 0.f;
-        }
-        if (sub == 0)
-            for (int kk = D; kk < Dp; ++kk) qs[kk * QT + j] = 0.f;
-        for (int i = tid; i < 4 * QT * kp; i += 256) { ls[i] = i % kp < k ? -INFINITY : INFINITY; li[i] = -1; }
-    }
+    cos_tile::load_tile<true>(qs, queries, qt * QT, Q, D);      // raw queries in, unit rows out; a zero query is a zero row
+    for (int i = tid; i < 4 * QT * kp; i += 256) { ls[i] = i % kp < k ? -INFINITY : INFINITY; li[i] = -1; }
     __syncthreads();
 
     float* my_s = ls + (w * QT + c) * kp;        // the list of (this wave, query c): shared by the lanes c and c + 32, which take turns
     const bool my_q = qt * QT + c < Q;           // the tile's columns past Q are zero queries: nothing is kept for them
     int* my_i = li + (w * QT + c) * kp;
-    const int ngroups = D >> 3;
-    for (int sl = 0; sl < slabs_per_wg; ++sl) {
-        const int r0 = (range * slabs_per_wg + sl) * SLAB + w * 32;
-        if (r0 >= U) break;                     // wave-uniform
-        const int row = r0 + c < U ? r0 + c : U - 1;       // rows past U are computed from row U - 1 and never inserted
-        const float* a = G + (size_t)row * D + 4 * half;
-        f32x16 acc;
-#pragma unroll
-        for (int v = 0; v < 16; ++v) acc[v] = 0.f;
-        int g = 0;
-        for (; g + 8 <= ngroups; g += 8) {      // 8 loads (64 k of 32 rows) in flight per wave before the first product
-            float4 v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const float4*>(a + (size_t)(g + u) * 8);
-            __builtin_amdgcn_sched_barrier(0);  // keep the eight loads ahead of the products (the scheduler otherwise sinks them in pairs)
-#pragma unroll
-            for (int u = 0; u < 8; ++u) mma_group<true>(v[u], qs + (size_t)(g + u) * 8 * QT, c, half, acc);
-        }
-        for (; g < ngroups; ++g) {
-            const float4 v = *reinterpret_cast<const float4*>(a + (size_t)g * 8);
-            mma_group<true>(v, qs + (size_t)g * 8 * QT, c, half, acc);
-        }
-        if (D & 4) {                            // the upper half's four k lie past the row: not read
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (half == 0) v = *reinterpret_cast<const float4*>(a + (size_t)ngroups * 8);
-            mma_group<false>(v, qs + (size_t)ngroups * 8 * QT, c, half, acc);
-        }
-        // acc[v] = score of row r0 + 8 (v / 4) + 4 half + v % 4 against query c
+    cos_tile::walk<int>(qs, G, U, D, range, slabs_per_wg, [&](int r0, const cos_tile::f32x16& acc) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             if (half == h) {
@@ -234,7 +159,7 @@ __global__ __launch_bounds__(256) void gallery_score_kernel(const float* __restr
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");     // the other half reads what this one wrote
             __builtin_amdgcn_wave_barrier();
         }
-    }
+    });
     __syncthreads();
     {   // the query's 4 k entries (unordered) -> the workgroup's ONE list, in order.  Eight lanes per query; an entry's place is its RANK,
         // the number of entries that beat it (the order is total: rows are distinct), so nothing is exchanged between lanes or rounds

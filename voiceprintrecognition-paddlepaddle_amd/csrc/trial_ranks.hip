@@ -1,12 +1,9 @@
 // EER / minDCF without the (Nt, Ne) score matrix (PPVectorTrainer.evaluate, trainer.py:416-431, and metric/metrics.py:4-37): the sorted
 // target scores and, for every gap between two of them, HOW MANY non-target scores fall into it.  docs/trial_ranks.md has the method.
 //
-// vp_trial_ranks_targets_f32  unit_rows_kernel writes both sides as unit rows into the workspace (a wave per row, the length in float64:
-//                             one rounding per element, the arithmetic of gallery.hip); then the targets pass.
-// trial_pass_kernel<MODE>     gallery_score_kernel's tile walk: a workgroup holds 32 unit trial rows in LDS ([k][trial], the B operand of
-//                             v_mfma_f32_32x32x2_f32) and walks `slabs_per_wg` slabs of 128 enrol rows, a wave per 32 rows, the 32 x 32
-//                             scores in one accumulator over ALL of D.  A score is one k-ordered fma chain whatever the tile, the wave,
-//                             the grid or the row's position: bit-identical rows give bit-identical scores, in every pass.
+// vp_trial_ranks_targets_f32  unit_rows_kernel writes both sides as unit rows into the workspace (a wave per row); then the targets pass.
+// trial_pass_kernel<MODE>     a workgroup holds 32 unit trial rows in LDS and walks `slabs_per_wg` slabs of enrol rows with cos_tile.h's
+//                             walk, which states how a score is summed and why a pair has the same bits in every pass.
 //                             The passes differ in what a lane does with its 16 scores:
 //   TARGETS  a pair with equal labels writes its score to targets[trial_offset[i] + enroll_rank[j]]: a place the labels alone fix.
 //   COUNTS   a pair with different labels finds its bin #{j : t[j] < s} in the sorted targets -- all of them in LDS when they fit,
@@ -16,15 +13,13 @@
 //   SELECT   a pair with different labels and lo < s <= hi whose order-preserving key agrees with `prefix` above the digit in hand
 //            counts that digit (11, 11 and 10 bits: an LDS histogram of 2048 counters; 65 536 would not fit beside the tile).
 // Integer counts only: no float atomics, no grid barrier, no spinning; the result does not depend on arrival order.
-#include "common.h"
-
-#include <math.h>
+#include "cos_tile.h"
 
 namespace {
 
-constexpr int SLAB = 128;               // 4 waves x 32 rows
-constexpr int QT = 32;                  // trials of a tile = the matrix core's N
-constexpr int MAX_D = 1024;
+using cos_tile::SLAB;
+using cos_tile::MAX_D;
+constexpr int QT = cos_tile::COLS;      // trials of a tile
 constexpr long long MAX_NT = 1LL << 24;
 constexpr int MAX_LDS = 160 * 1024;
 constexpr int PIVOTS = 2048;            // two-level search: at most this many pivots in LDS
@@ -32,8 +27,6 @@ constexpr int DIGIT_BINS = 2048;
 constexpr int MAX_SLABS_PER_WG = 1 << 16;       // 32 x 128 x 2^16 = 2^28 pairs per workgroup: a 32-bit LDS count cannot wrap
 
 enum { TARGETS = 0, COUNTS = 1, SELECT = 2 };
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 bool supported(int Nt, int Ne, int D, long long NT) {
     return Nt >= 1 && Ne >= 1 && D >= 4 && D % 4 == 0 && D <= MAX_D && NT >= 1 && NT <= MAX_NT;
@@ -78,8 +71,7 @@ Plan plan(int Nt, int Ne, int D, long long NT) {
 }
 
 // ------------------------------------------------------------------------------------------------ unit rows
-// A wave per row, 16-byte loads.  The length in float64, 1 / sqrt exactly rounded: a unit row is rounded once per element; a zero row
-// stays zero.
+// A wave per row, 16-byte loads; the length as cos_tile.h takes it, summed over the wave's lanes.
 __global__ __launch_bounds__(256) void unit_rows_kernel(const float* __restrict__ x, long long rows, int D, float* __restrict__ y) {
     const int lane = threadIdx.x & 63;
     const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -87,20 +79,15 @@ __global__ __launch_bounds__(256) void unit_rows_kernel(const float* __restrict_
     const float* src = x + (size_t)r * D;
     float* dst = y + (size_t)r * D;
     double ss = 0.0;
-    for (int k = lane * 4; k < D; k += 256) {
-        const float4 v = *reinterpret_cast<const float4*>(src + k);
-        ss += (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
-    }
+    for (int k = lane * 4; k < D; k += 256) ss += cos_tile::sum_sq(*reinterpret_cast<const float4*>(src + k));
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
-    const double inv = ss > 0.0 ? 1.0 / sqrt(ss) : 0.0;
-    for (int k = lane * 4; k < D; k += 256) {
-        const float4 v = *reinterpret_cast<const float4*>(src + k);
-        *reinterpret_cast<float4*>(dst + k) = make_float4((float)(v.x * inv), (float)(v.y * inv), (float)(v.z * inv), (float)(v.w * inv));
-    }
+    const double inv = cos_tile::inv_length(ss);
+    for (int k = lane * 4; k < D; k += 256)
+        *reinterpret_cast<float4*>(dst + k) = cos_tile::scale4(*reinterpret_cast<const float4*>(src + k), inv);
 }
 
-// ------------------------------------------------------------------------------------------------ the tile walk
+// ------------------------------------------------------------------------------------------------ the passes
 struct PassArgs {
     const float* tu;                    // (Nt, D) unit trial rows
     const float* eu;                    // (Ne, D) unit enrol rows
@@ -124,20 +111,6 @@ struct PassArgs {
     unsigned long long* hist;
 };
 
-// Eight consecutive k of the wave's 32 rows x the tile's 32 trials (gallery.hip's mma_group: lane (c, half) holds k0 + 4 half + {0..3}
-// of its row in v; the swaps leave (k0, k0 + 1), (k0 + 2, k0 + 3), (k0 + 4, k0 + 5), (k0 + 6, k0 + 7) on the two halves of x, z, y, w).
-template <bool FULL>
-__device__ __forceinline__ void mma_group(float4 v, const float* __restrict__ qb, int c, int half, f32x16& acc) {
-    const auto xy = __builtin_amdgcn_permlane32_swap(__float_as_uint(v.x), __float_as_uint(v.y), false, false);
-    const auto zw = __builtin_amdgcn_permlane32_swap(__float_as_uint(v.z), __float_as_uint(v.w), false, false);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(xy[0]), qb[(0 + half) * QT + c], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(zw[0]), qb[(2 + half) * QT + c], acc, 0, 0, 0);
-    if (FULL) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(xy[1]), qb[(4 + half) * QT + c], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(zw[1]), qb[(6 + half) * QT + c], acc, 0, 0, 0);
-    }
-}
-
 // #{i < n : a[i] < s}, a ascending
 __device__ __forceinline__ int count_below(const float* a, int n, float s) {
     int lo = 0;
@@ -146,12 +119,6 @@ __device__ __forceinline__ int count_below(const float* a, int n, float s) {
         if (a[lo + h] < s) { lo += h + 1; n -= h + 1; } else n = h;
     }
     return lo;
-}
-
-// a float's bits as an unsigned that orders as the float does
-__device__ __forceinline__ unsigned order_key(float s) {
-    const unsigned u = __float_as_uint(s);
-    return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
 }
 
 // grid (trial tiles, row ranges), 256 threads, dynamic LDS: qs [Dp][32] | COUNTS: pivots [P], counts [H] | SELECT: counts [DIGIT_BINS]
@@ -163,27 +130,13 @@ __global__ __launch_bounds__(256) void trial_pass_kernel(const PassArgs a) {
     float* piv = smem + (size_t)Dp * QT;
     unsigned* cnt = reinterpret_cast<unsigned*>(piv + (MODE == COUNTS ? a.P : 0));
     const int nbins = MODE == COUNTS ? a.H : (MODE == SELECT ? DIGIT_BINS : 0);
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 31, half = lane >> 5;
+    const int tid = threadIdx.x, lane = tid & 63, c = lane & 31, half = lane >> 5;
     const int qt = blockIdx.x, range = blockIdx.y;
 
-    {   // the trial tile: eight threads per trial, 16-byte loads; trials past Nt and the k past D are zero
-        const int j = tid >> 3, sub = tid & 7;
-        const int q = qt * QT + j;
-        const bool qv = q < a.Nt;
-        const float* src = a.tu + (size_t)(qv ? q : 0) * D;
-        for (int kk = sub * 4; kk < D; kk += 32) {
-            const float4 v = *reinterpret_cast<const float4*>(src + kk);
-            qs[(kk + 0) * QT + j] = qv ? v.x : 0.f;
-            qs[(kk + 1) * QT + j] = qv ? v.y : 0.f;
-            qs[(kk + 2) * QT + j] = qv ? v.z : 0.f;
-            qs[(kk + 3) * QT + j] = qv ? v.w : 0.f;
-        }
-        if (sub == 0)
-            for (int kk = D; kk < Dp; ++kk) qs[kk * QT + j] = 0.f;
-        if (MODE == COUNTS)
-            for (int i = tid; i < a.P; i += 256) piv[i] = a.st[(size_t)i * a.stride];       // i stride < NT: P = ceil(NT / stride)
-        for (int i = tid; i < nbins; i += 256) cnt[i] = 0u;
-    }
+    cos_tile::load_tile<false>(qs, a.tu, qt * QT, a.Nt, D);
+    if (MODE == COUNTS)
+        for (int i = tid; i < a.P; i += 256) piv[i] = a.st[(size_t)i * a.stride];           // i stride < NT: P = ceil(NT / stride)
+    for (int i = tid; i < nbins; i += 256) cnt[i] = 0u;
     __syncthreads();
 
     const int q = qt * QT + c;
@@ -191,34 +144,7 @@ __global__ __launch_bounds__(256) void trial_pass_kernel(const PassArgs a) {
     const int lq = my_q ? a.tl[q] : 0;
     long long off = 0;
     if (MODE == TARGETS && my_q) off = a.toff[q];
-    const int ngroups = D >> 3;
-    for (int sl = 0; sl < a.slabs_per_wg; ++sl) {
-        const long long r0 = ((long long)range * a.slabs_per_wg + sl) * SLAB + w * 32;
-        if (r0 >= a.Ne) break;          // wave-uniform
-        const long long row = r0 + c < a.Ne ? r0 + c : a.Ne - 1;    // rows past Ne are computed from row Ne - 1 and never used
-        const float* e = a.eu + (size_t)row * D + 4 * half;
-        f32x16 acc;
-#pragma unroll
-        for (int v = 0; v < 16; ++v) acc[v] = 0.f;
-        int g = 0;
-        for (; g + 8 <= ngroups; g += 8) {      // 8 loads (64 k of 32 rows) in flight per wave before the first product
-            float4 v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const float4*>(e + (size_t)(g + u) * 8);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int u = 0; u < 8; ++u) mma_group<true>(v[u], qs + (size_t)(g + u) * 8 * QT, c, half, acc);
-        }
-        for (; g < ngroups; ++g) {
-            const float4 v = *reinterpret_cast<const float4*>(e + (size_t)g * 8);
-            mma_group<true>(v, qs + (size_t)g * 8 * QT, c, half, acc);
-        }
-        if (D & 4) {                            // the upper half's four k lie past the row: not read
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (half == 0) v = *reinterpret_cast<const float4*>(e + (size_t)ngroups * 8);
-            mma_group<false>(v, qs + (size_t)ngroups * 8 * QT, c, half, acc);
-        }
-        // acc[v] = score of enrol row r0 + 8 (v / 4) + 4 half + v % 4 against trial c
+    cos_tile::walk<long long>(qs, a.eu, a.Ne, D, range, a.slabs_per_wg, [&](long long r0, const cos_tile::f32x16& acc) {
         const long long rb = r0 + 4 * half;
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
@@ -243,11 +169,11 @@ __global__ __launch_bounds__(256) void trial_pass_kernel(const PassArgs a) {
                 else atomicAdd(&a.hist[bin], 1ull);
             } else {
                 if (same || !(s > a.lo && s <= a.hi)) continue;
-                const unsigned key = order_key(s);
+                const unsigned key = vp_order_key(s);
                 if ((key & a.prefix_mask) == a.prefix) atomicAdd(&cnt[(key >> a.shift) & a.digit_mask], 1u);
             }
         }
-    }
+    });
     if (MODE != TARGETS) {
         __syncthreads();
         for (int b = tid; b < nbins; b += 256) {
