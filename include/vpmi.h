@@ -719,9 +719,28 @@ int vp_sphereface2(vp_ctx* ctx, const float* logits, const int64_t* labels, cons
  * vp_affine_rows_f32: y = z * scale + shift (then ReLU when relu: the conv -> BN -> ReLU order of the 2-D models).   vp_bn_relu_bwd_f32: dz through BN (batch statistics) and the ReLU before it.
  * vp_adam_step_f32: Adam with coupled L2 (optimizer/__init__.py:12-18), bias-corrected, on a flat f32 buffer.
  * ---------------------------------------------------------------------------------------------- */
+/* vp_conv1d_wgrad_workspace_bytes: the workspace of every weight-gradient entry point below (csrc/wgrad.hip).  The count depends on
+ *   the GEOMETRY only -- B, T_out, F_out / 2-D-ness (KF, F_in, F_out), Cout, Cin, KW -- and not on dtype_in, mfma_bf16, any pointer
+ *   or any pitch: a caller may size the workspace before it sets the operand type.  A batched launch needs nbatch x that.  A
+ *   workspace one byte short is VP_EWORKSPACE before any launch. */
 size_t vp_conv1d_wgrad_workspace_bytes(const vp_conv1d_desc* d);
 int vp_conv1d_wgrad_f32(vp_ctx* ctx, const vp_conv1d_desc* d, const float* dz, int lddz, float* dW, void* ws, size_t ws_bytes,
                         vp_stream stream);
+/* vp_conv1d_wgrad_plan: the launch a weight-gradient entry point makes for this descriptor, dz, lddz and nbatch (1, or the count of
+ *   vp_conv1d_wgrad_bf16_oik_batched) on a chip of `cus` compute units (<= 0: 256), host only (no device call; d->x and dz are
+ *   checked for NULL and for 16-byte alignment and never dereferenced).  Runs the launch's validation except the workspace check and
+ *   the same plan function, and returns what the launch would return up to there.  On VP_OK: *kernel = the kernel family
+ *   (VP_WGRAD_*), a dW tile of *tile_n outputs x *tile_k columns of K = KW * Cin, the rows cut into *splits splits of
+ *   *rows_per_split rows (whole staged chunks, none empty), *splits partial [Cout][K] arrays in the workspace per conv.  Any output
+ *   pointer may be NULL; on an error the outputs are left alone.  VPMI_WGRAD_TR256_OFF (read once per process) keeps every layer
+ *   off VP_WGRAD_TR256. */
+enum { VP_WGRAD_F32 = 0,     /* exact f32, 64 x 64 tiles                                  */
+       VP_WGRAD_AMP = 1,     /* bf16 matrix cores, 128 x 128 tiles, f32 or bf16 operands  */
+       VP_WGRAD_X3 = 2,      /* split precision, 128 x 128 tiles, one workgroup per CU    */
+       VP_WGRAD_N64 = 3,     /* bf16 operands, Cout <= 64: 64 x 256 tiles                 */
+       VP_WGRAD_TR256 = 4 }; /* bf16 operands, wide 1x1 layers: 256 x 256, transposing LDS reads */
+int vp_conv1d_wgrad_plan(const vp_conv1d_desc* d, const void* dz, int lddz, int nbatch, int cus,
+                         int* kernel, int* tile_n, int* tile_k, int* splits, int* rows_per_split);
 /* vp_conv1d_wgrad_oik_f32: the same gradient reduced straight into the model's (Cout, Cin, KW) layout (utils.py:22-93 stores
  * nn.Conv1D weights that way).  vp_conv_weight_layouts_f32: from that tensor, the forward weight panel wp (Cout, KW * Cin) and the
  * data-gradient panel w2 (Cin, KW * Cout; taps reversed, channel roles swapped) in one launch; either output may be NULL. */

@@ -1279,9 +1279,10 @@ def test_col_sums_kernel_vs_float64(N, M, C, two):
                                                   # round 5: a 128-column side on the 256-tile kernel (ASP's attention TDNN and logits conv at 256 x 298 frames)
                                                   (76288, 128, 1536, 1536, 0), (76288, 1536, 128, 128, 0), (76289, 128, 1536, 1800, 264)])
 def test_wgrad_of_bf16_operands_vs_float64(N, M, Cout, Cin, ldx, xoff):
-    """vp_conv1d_wgrad_bf16_oik on the wide 1x1 layers: the 256-tile kernel on transposing LDS reads (csrc/wgrad_tr.hip; the last case has
-    Cout % 256 != 0 and runs the 128-tile kernel).  bf16 products are exact in f32, so the only error is the f32 accumulation order:
-    1e-5 of sum |dz| |x| per output (measured ~1e-6); twenty launches are bit-identical."""
+    """vp_conv1d_wgrad_bf16_oik on the wide 1x1 layers: the 256-tile kernel on transposing LDS reads (csrc/wgrad.hip: VP_WGRAD_TR256) for
+    the four cases of 76 288 / 76 289 rows, the 128-tile kernel (VP_WGRAD_AMP) for the case with Cout % 256 != 0 and for the ones under
+    the 256-tile kernel's 3e10-flop gate; vp_conv1d_wgrad_plan must say so.  bf16 products are exact in f32, so the only error is the
+    f32 accumulation order: 1e-5 of sum |dz| |x| per output (measured ~1e-6); twenty launches are bit-identical."""
     import ctypes as C
     lib, ctx = N.lib(), N.ctx(torch.device('cuda', 0))
     g = torch.Generator().manual_seed(M + Cout)
@@ -1295,6 +1296,9 @@ def test_wgrad_of_bf16_operands_vs_float64(N, M, Cout, Cin, ldx, xoff):
     d.x, d.ldx, d.xoff = xd.data_ptr(), ldx, xoff
     d.mfma_bf16 = 1
     ws = torch.empty(lib.vp_conv1d_wgrad_workspace_bytes(C.byref(d)), dtype=torch.uint8, device='cuda')
+    family = C.c_int(-1)
+    N.check(lib.vp_conv1d_wgrad_plan(C.byref(d), dzd.data_ptr(), Cout, 1, 0, C.byref(family), None, None, None, None), ctx)
+    assert family.value == (N.VP_WGRAD_TR256 if M >= 76288 else N.VP_WGRAD_AMP), family.value
     outs = []
     for _ in range(20):
         dW = torch.full((Cout, Cin), float('nan'), dtype=torch.float32, device='cuda')
@@ -1345,6 +1349,7 @@ def test_wgrad_split_precision_vs_float64(N, case):
         res[mode] = ((dW.double().cpu() - ref).norm() / ref.norm()).item()
     print(f'[wgrad {case}] rel-L2 vs float64: exact f32 {res[0]:.2e}, split precision {res[2]:.2e}, one bf16 pass {res[1]:.2e}')
     assert res[2] < 2e-5 and res[1] > 30 * res[2], res
+    assert res[0] < 3e-5, res                                          # exact f32 (conv_wgrad_kernel): the bound test_conv2d_wgrad_vs_float64 holds mode 0 to
 
 
 @pytest.mark.parametrize('M,C,relu,gamma', [(76288, 512, 1, True), (4097, 64, 1, True), (300, 128, 0, True), (1000, 1536, 1, False),

@@ -1,4 +1,4 @@
-"""Weight-gradient kernels of the wide 1x1 layers, timed in isolation: the 256-tile kernel on transposing LDS reads (csrc/wgrad_tr.hip)
+"""Weight-gradient kernels of the wide 1x1 layers, timed in isolation: the 256-tile kernel on transposing LDS reads (VP_WGRAD_TR256 of csrc/wgrad.hip)
 against the 128-tile register-transpose kernel (VPMI_WGRAD_TR256_OFF=1, a second process).  Usage: python tools/wgrad_probe.py [reps]"""
 import ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

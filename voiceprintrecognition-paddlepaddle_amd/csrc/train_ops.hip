@@ -1,499 +1,16 @@
-// Training-side kernels (f32 engine): conv weight gradient, Adam, gradient packing, the per-utterance (ASP) and CAM++ context pieces.
-// BatchNorm with batch statistics and the column sums are in bn_train.hip.
+// Training-side kernels (f32 engine): the conv weight layouts and bf16 weight panels, Adam, momentum, gradient packing, the
+// per-utterance (ASP) and CAM++ context pieces and the activations.  The conv weight gradient (and the partial-sum reducer other
+// files borrow) is in wgrad.hip; BatchNorm with batch statistics and the column sums are in bn_train.hip.
 //
 // Reference: what paddle's autograd + optimiser run for PPVectorTrainer.__train_epoch (ppvector/trainer.py:202-274):
-// Conv1D backward (models/utils.py:65-93 layers), BatchNorm1D in train mode (utils.py:96-119: batch statistics over
-// (B, T); running = 0.9 running + 0.1 batch), ReLU, and Adam with coupled L2 (optimizer/__init__.py:12-18,
-// configs/*.yml weight_decay 1e-6).  Activations are position-major (M = B*T rows, C contiguous) like everywhere else;
-// every reduction is two-stage and fixed-order (no atomics): results are bit-reproducible run to run.
+// the layers of models/utils.py:65-148, ReLU, and Adam with coupled L2 (optimizer/__init__.py:12-18, configs/*.yml weight_decay
+// 1e-6).  Activations are position-major (M = B*T rows, C contiguous) like everywhere else; every reduction is two-stage and
+// fixed-order (no atomics): results are bit-reproducible run to run.
 #include "common.h"
 
 namespace {
 
-// ---------------------------------------------------------------------------------------------- conv weight gradient
-// dW[n][j*Cin + c] = sum_{b,t} dz[b, t, n] * x[b, src(t, j), c],  src = the forward's tap index (reflect / zero / none).
-// One workgroup = a 64 (n) x 64 (k-column) tile of dW over a slice of the rows; 4 waves of 32 x 32; v_mfma_f32_16x16x4_f32
-// with dz^T as the A operand and the shifted x rows as B -- both operands are read row-wise (16 lanes = 64 contiguous
-// bytes), the reduction dimension (rows) is the MFMA k.  Partials [S][Cout][K] are summed by wgrad_reduce_kernel.
-struct WgradArgs {
-    const float* x; const float* dz; float* part;
-    int ldx, xoff, lddz, M, N, K, Cin, T_in, T_out, dilation, stride, pad_left, pad_mode, rows_per_split;
-    int F_in, F_out, KF, stride_f, pad_f;        // 2-D convs (zero padding): rows are (b, t, f), taps (kt, kf); F_in = F_out = KF = 1 for 1-D
-    // batched launch (amp kernel): blockIdx.z = conv * splits + split; conv c reads x + c * xb, dz + c * dzb (elements of their dtype)
-    int splits; long long xb, dzb;
-};
-
-// LDS-tiled: per 32-row chunk the workgroup stages dz[32][64 n] and the tap-shifted x[32][64 k-columns] with 16-byte loads
-// (16 lanes per row, prefetched one chunk ahead in registers), then every wave reads its MFMA operands from LDS
-// (row stride 80 floats: the four k-rows of a fragment land on disjoint banks).  The first version fetched every
-// fragment straight from global memory, 4 bytes per lane: 53 TFLOP/s on the 1536 x 1536 layer.
-constexpr int WG_RC = 32;              // rows per staged chunk
-constexpr int WG_LD = 80;              // floats per staged row (64 + 16 pad)
-
-__global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradArgs a) {
-    __shared__ __attribute__((aligned(16))) float dzs[WG_RC * WG_LD];
-    __shared__ __attribute__((aligned(16))) float xs[WG_RC * WG_LD];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int i = lane & 15, kk = lane >> 4;
-    const int wn = wv & 1, wk = wv >> 1;
-    const int nb = blockIdx.y * 64, kb = blockIdx.x * 64;
-    const int m_begin = blockIdx.z * a.rows_per_split;
-    const int m_end = min(a.M, m_begin + a.rows_per_split);
-    // staging role: rows srow and srow + 16 of the chunk, 4 consecutive columns starting at scol
-    const int srow = tid >> 4, scol = (tid & 15) * 4;
-    const int ncol = nb + scol;                       // dz column (4 consecutive n; N % 4 == 0 -> all or none valid)
-    const bool nvalid = ncol < a.N;
-    const int kcol = kb + scol;                       // k-column = tap * Cin + c (Cin % 4 == 0: the 4 stay inside one tap)
-    const bool kvalid = kcol < a.K;
-    const int j = kvalid ? kcol / a.Cin : 0;
-    const int cc = kvalid ? kcol - j * a.Cin : 0;
-    const int kt = j / a.KF;
-    const int tapoff = kt * a.dilation - a.pad_left, tapf = (j - kt * a.KF) - a.pad_f;
-    const bool vec_ok = (a.Cin & 3) == 0 && ((a.ldx | a.xoff) & 3) == 0 && (a.lddz & 3) == 0;
-
-    float4 rdz[2], rx[2];
-    auto gload = [&](int mbase) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int m = mbase + srow + 16 * h;
-            rdz[h] = make_float4(0.f, 0.f, 0.f, 0.f);
-            rx[h] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (m >= m_end) continue;
-            if (nvalid) rdz[h] = *reinterpret_cast<const float4*>(a.dz + (size_t)m * a.lddz + ncol);
-            if (kvalid) {
-                const int bt = m / a.F_out, f = m - bt * a.F_out;
-                const int b = bt / a.T_out, t = bt - b * a.T_out;
-                const int traw = t * a.stride + tapoff, fs = f * a.stride_f + tapf;
-                int ts = traw;
-                bool ok = fs >= 0 && fs < a.F_in;
-                if (a.pad_mode == VP_PAD_REFLECT) {
-                    ts = ts < 0 ? -ts : ts;
-                    ts = ts >= a.T_in ? 2 * (a.T_in - 1) - ts : ts;
-                } else {
-                    ok = ok && traw >= 0 && traw < a.T_in;
-                }
-                if (ok) rx[h] = *reinterpret_cast<const float4*>(a.x + (((size_t)b * a.T_in + ts) * a.F_in + fs) * a.ldx + a.xoff + cc);
-            }
-        }
-    };
-    auto swrite = [&]() {
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            *reinterpret_cast<float4*>(dzs + (srow + 16 * h) * WG_LD + scol) = rdz[h];
-            *reinterpret_cast<float4*>(xs + (srow + 16 * h) * WG_LD + scol) = rx[h];
-        }
-    };
-    f32x4 acc[2][2];
-#pragma unroll
-    for (int p = 0; p < 2; ++p)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) acc[p][q] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (!vec_ok) return;                              // host refuses these shapes (kept so the kernel cannot misread)
-    gload(m_begin);
-    for (int mb = m_begin; mb < m_end; mb += WG_RC) {
-        swrite();
-        __syncthreads();
-        gload(mb + WG_RC);                            // rows past m_end come back as zeros
-#pragma unroll
-        for (int r = 0; r < WG_RC; r += 4) {
-            float av[2], bv[2];
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                av[q] = dzs[(r + kk) * WG_LD + wn * 32 + q * 16 + i];
-                bv[q] = xs[(r + kk) * WG_LD + wk * 32 + q * 16 + i];
-            }
-#pragma unroll
-            for (int p = 0; p < 2; ++p)
-#pragma unroll
-                for (int q = 0; q < 2; ++q) acc[p][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[p], bv[q], acc[p][q], 0, 0, 0);
-        }
-        __syncthreads();
-    }
-    const int n0 = nb + wn * 32, k0 = kb + wk * 32;
-    float* out = a.part + (size_t)blockIdx.z * a.N * a.K;
-#pragma unroll
-    for (int p = 0; p < 2; ++p)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const int col = k0 + q * 16 + i;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int n = n0 + p * 16 + kk * 4 + r;
-                if (n < a.N && col < a.K) out[(size_t)n * a.K + col] = acc[p][q][r];
-            }
-        }
-}
-
-// Mixed precision (vp_conv1d_desc.mfma_bf16): the same contraction on the bf16 matrix cores.  One workgroup = a 128 (n) x 128
-// (k-column) tile of dW over a slice of the rows, 4 waves of 64 x 64 (v_mfma_f32_16x16x32_bf16, f32 accumulate).  The reduction
-// index is the ROW, along which both operands are strided in memory: a thread loads 8 rows x 4 consecutive columns (16-byte
-// loads, a half-wave = 512 contiguous bytes of a row), rounds to bf16 and writes the four 8-row column pieces TRANSPOSED into
-// LDS ([column][64 rows], 128 B per column), where a fragment is one ds_read_b128.  The 16-byte chunk q of column R sits at
-// position q ^ L(R), L(R) = ((R >> 1) & 7) ^ ((R >> 4) & 1): conflict-free for the transposed writes (8 lanes = columns 4
-// apart) AND for the fragment reads (searched exhaustively over XOR-linear maps against the ds_read_b128 lane groups).
-constexpr int WA_T = 128;              // tile edge of dW
-constexpr int WA_RC = 64;              // rows per staged chunk = two MFMA k-steps
-__device__ __forceinline__ int wa_L(int R) { return ((R >> 1) & 7) ^ ((R >> 4) & 1); }
-
-// BF: x and dz are already bf16 in memory (the wide layers' operands, see ConvBlock): 8-byte loads of four bf16, no rounding here.
-typedef __attribute__((ext_vector_type(8))) unsigned short u16x8;
-
-// X3 (f32 operands only): split precision -- each operand is staged as TWO transposed bf16 planes (hi = bf16(v), lo = bf16(v - hi)) and
-// the contraction is lo*hi + hi*lo + hi*hi (conv_gemm_impl.h: x3_t): the weight gradient of the 'float32x3' training mode, ~2^-17 per
-// product.  Twice the LDS (128 KB: one workgroup per CU) and three MFMAs per fragment pair.
-template <bool BF, bool X3 = false>
-__global__ __launch_bounds__(256, X3 ? 1 : 2) void conv_wgrad_amp_kernel(WgradArgs a) {
-    static_assert(!(BF && X3), "split precision takes f32 operands");
-    constexpr int PLANES = X3 ? 2 : 1;
-    constexpr int STG = PLANES * 2 * WA_T * 128;                       // bytes per stage
-    extern __shared__ __attribute__((aligned(16))) char wsm[];        // [2 stages][dz^T 16 KB | x^T 16 KB] (x3: + the two lo planes)
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int i = lane & 15, g = lane >> 4;
-    const int wn = wv & 1, wk = wv >> 1;
-    const int nb = blockIdx.y * WA_T, kb = blockIdx.x * WA_T;
-    const int zb = blockIdx.z / a.splits, sp = blockIdx.z - zb * a.splits;
-    const int m_begin = sp * a.rows_per_split;
-    const int m_end = min(a.M, m_begin + a.rows_per_split);
-    // staging role: rows 8 rg .. 8 rg + 7 of the chunk, columns 4 cg .. 4 cg + 3 of the tile
-    const int cg = tid & 31, rg = tid >> 5;
-    const int ncol = nb + 4 * cg;
-    const bool nvalid = ncol < a.N;
-    const int kcol = kb + 4 * cg;                     // k-column = tap * Cin + c (Cin % 4 == 0: the 4 stay inside one tap)
-    const bool kvalid = kcol < a.K;
-    const int j = kvalid ? kcol / a.Cin : 0;
-    const int cc = kvalid ? kcol - j * a.Cin : 0;
-    const int kt = j / a.KF;
-    const int tapoff = kt * a.dilation - a.pad_left, tapf = (j - kt * a.KF) - a.pad_f;
-    // 1x1 convs with identical input / output geometry (the wide layers): source row = output row
-    const bool simple = a.K == a.Cin && a.stride == 1 && a.pad_left == 0 && a.T_in == a.T_out && a.F_in == 1 && a.F_out == 1;
-
-    using ld_t = typename std::conditional<BF, uint2, float4>::type;
-    using el_t = typename std::conditional<BF, bf16_t, float>::type;
-    const el_t* __restrict__ gdz = reinterpret_cast<const el_t*>(a.dz) + zb * a.dzb;
-    const el_t* __restrict__ gx = reinterpret_cast<const el_t*>(a.x) + zb * a.xb;
-    ld_t rdz[8], rx[8];
-    auto gload = [&](int mbase) {
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            const int m = mbase + 8 * rg + r;
-            rdz[r] = ld_t{};
-            rx[r] = ld_t{};
-            if (m >= m_end) continue;
-            if (nvalid) rdz[r] = *reinterpret_cast<const ld_t*>(gdz + (size_t)m * a.lddz + ncol);
-            if (!kvalid) continue;
-            if (simple) {
-                rx[r] = *reinterpret_cast<const ld_t*>(gx + (size_t)m * a.ldx + a.xoff + cc);
-            } else {
-                const int bt = m / a.F_out, f = m - bt * a.F_out;
-                const int b = bt / a.T_out, t = bt - b * a.T_out;
-                const int traw = t * a.stride + tapoff, fs = f * a.stride_f + tapf;
-                int ts = traw;
-                bool ok = fs >= 0 && fs < a.F_in;
-                if (a.pad_mode == VP_PAD_REFLECT) {
-                    ts = ts < 0 ? -ts : ts;
-                    ts = ts >= a.T_in ? 2 * (a.T_in - 1) - ts : ts;
-                } else {
-                    ok = ok && traw >= 0 && traw < a.T_in;
-                }
-                if (ok) rx[r] = *reinterpret_cast<const ld_t*>(gx + (((size_t)b * a.T_in + ts) * a.F_in + fs) * a.ldx + a.xoff + cc);
-            }
-        }
-    };
-    auto swrite = [&](int s) {
-        char* dzs = wsm + s * STG;
-        char* xs = dzs + WA_T * 128;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int R = 4 * cg + e;
-            const int pos = (rg ^ wa_L(R)) << 4;
-            if constexpr (BF) {
-                u16x8 vd, vx;
-#pragma unroll
-                for (int r = 0; r < 8; ++r) {
-                    const unsigned wd = e < 2 ? rdz[r].x : rdz[r].y, wx = e < 2 ? rx[r].x : rx[r].y;
-                    vd[r] = (unsigned short)((e & 1) ? (wd >> 16) : (wd & 0xffffu));
-                    vx[r] = (unsigned short)((e & 1) ? (wx >> 16) : (wx & 0xffffu));
-                }
-                *reinterpret_cast<u16x8*>(dzs + R * 128 + pos) = vd;
-                *reinterpret_cast<u16x8*>(xs + R * 128 + pos) = vx;
-            } else {
-                bf16x8 vd, vx;
-                [[maybe_unused]] bf16x8 ld, lx;
-#pragma unroll
-                for (int r = 0; r < 8; ++r) {
-                    const float d = e == 0 ? rdz[r].x : (e == 1 ? rdz[r].y : (e == 2 ? rdz[r].z : rdz[r].w));
-                    const float xv = e == 0 ? rx[r].x : (e == 1 ? rx[r].y : (e == 2 ? rx[r].z : rx[r].w));
-                    vd[r] = (bf16_t)d;
-                    vx[r] = (bf16_t)xv;
-                    if constexpr (X3) {
-                        ld[r] = (bf16_t)(d - (float)vd[r]);
-                        lx[r] = (bf16_t)(xv - (float)vx[r]);
-                    }
-                }
-                *reinterpret_cast<bf16x8*>(dzs + R * 128 + pos) = vd;
-                *reinterpret_cast<bf16x8*>(xs + R * 128 + pos) = vx;
-                if constexpr (X3) {
-                    *reinterpret_cast<bf16x8*>(dzs + 2 * WA_T * 128 + R * 128 + pos) = ld;
-                    *reinterpret_cast<bf16x8*>(xs + 2 * WA_T * 128 + R * 128 + pos) = lx;
-                }
-            }
-        }
-    };
-    f32x4 acc[4][4];
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc[p][q] = f32x4{0.f, 0.f, 0.f, 0.f};
-    gload(m_begin);
-    int s = 0;
-    for (int mb = m_begin; mb < m_end; mb += WA_RC) {
-        swrite(s);
-        __syncthreads();
-        gload(mb + WA_RC);                            // rows past m_end come back as zeros
-        const char* dzs = wsm + s * STG;
-        const char* xs = dzs + WA_T * 128;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            bf16x8 af[4], bf[4];
-            [[maybe_unused]] bf16x8 al[4], bl[4];
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                const int R = wn * 64 + p * 16 + i;
-                af[p] = *reinterpret_cast<const bf16x8*>(dzs + R * 128 + (((ks * 4 + g) ^ wa_L(R)) << 4));
-                if constexpr (X3) al[p] = *reinterpret_cast<const bf16x8*>(dzs + 2 * WA_T * 128 + R * 128 + (((ks * 4 + g) ^ wa_L(R)) << 4));
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int R = wk * 64 + q * 16 + i;
-                bf[q] = *reinterpret_cast<const bf16x8*>(xs + R * 128 + (((ks * 4 + g) ^ wa_L(R)) << 4));
-                if constexpr (X3) bl[q] = *reinterpret_cast<const bf16x8*>(xs + 2 * WA_T * 128 + R * 128 + (((ks * 4 + g) ^ wa_L(R)) << 4));
-            }
-#pragma unroll
-            for (int p = 0; p < 4; ++p)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    if constexpr (X3) {
-                        acc[p][q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[p], bf[q], acc[p][q], 0, 0, 0);
-                        acc[p][q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[p], bl[q], acc[p][q], 0, 0, 0);
-                    }
-                    acc[p][q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[p], bf[q], acc[p][q], 0, 0, 0);
-                }
-        }
-        s ^= 1;
-    }
-    const int n0 = nb + wn * 64, k0 = kb + wk * 64;
-    float* out = a.part + (size_t)blockIdx.z * a.N * a.K;
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int col = k0 + q * 16 + i;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int n = n0 + p * 16 + g * 4 + r;
-                if (n < a.N && col < a.K) out[(size_t)n * a.K + col] = acc[p][q][r];
-            }
-        }
-}
-
-// The same contraction for a NARROW layer: N <= 64 outputs (the Res2Net chunk convs: 64 x 192; the 32- and 64-channel 2-D convs of
-// ResNetSE / ERes2Net on their largest feature maps).  The square 128 x 128 tile above spends up to 3/4 of its MFMAs and LDS traffic on
-// output rows that do not exist there; here a workgroup takes all N <= 64 outputs x 256 k-columns (blockIdx.x), the four waves 64
-// k-columns each.  LDS: 2 stages x (dz^T 64 x 128 B | x^T 256 x 128 B).  BF: bf16 operands in memory (1-D only, as the caller has them);
-// else f32 operands rounded on the way in, 1-D or 2-D taps as in the kernel above.
-__device__ __forceinline__ uint2 wg_pack4(float4 v) {
-    bf16x4 o;
-    o[0] = (bf16_t)v.x; o[1] = (bf16_t)v.y; o[2] = (bf16_t)v.z; o[3] = (bf16_t)v.w;
-    return __builtin_bit_cast(uint2, o);
-}
-template <bool BF>
-__global__ __launch_bounds__(256, 2) void conv_wgrad_n64_kernel(WgradArgs a) {
-    extern __shared__ __attribute__((aligned(16))) char wsm[];
-    constexpr int STAGE = (64 + 256) * 128;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int i = lane & 15, g = lane >> 4;
-    const int kb = blockIdx.x * 256;
-    const int zb = blockIdx.z / a.splits, sp = blockIdx.z - zb * a.splits;
-    const int m_begin = sp * a.rows_per_split;
-    const int m_end = min(a.M, m_begin + a.rows_per_split);
-    const int cg = tid & 31, rg = tid >> 5;
-    const bool nvalid = cg < 16 && 4 * cg < a.N;
-    int cc[2], tapoff[2], tapf[2];
-    bool kvalid[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        const int kcol = kb + 128 * u + 4 * cg;
-        kvalid[u] = kcol < a.K;
-        const int j = kvalid[u] ? kcol / a.Cin : 0;
-        cc[u] = kvalid[u] ? kcol - j * a.Cin : 0;
-        const int kt = j / a.KF;
-        tapoff[u] = kt * a.dilation - a.pad_left;
-        tapf[u] = (j - kt * a.KF) - a.pad_f;
-    }
-    uint2 rdz[8], rx[2][8];
-    auto gload = [&](int mbase) {
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            const int m = mbase + 8 * rg + r;
-            rdz[r] = uint2{0u, 0u}; rx[0][r] = uint2{0u, 0u}; rx[1][r] = uint2{0u, 0u};
-            if (m >= m_end) continue;
-            if (nvalid) {
-                if constexpr (BF) rdz[r] = *reinterpret_cast<const uint2*>(reinterpret_cast<const bf16_t*>(a.dz) + zb * a.dzb + (size_t)m * a.lddz + 4 * cg);
-                else rdz[r] = wg_pack4(*reinterpret_cast<const float4*>(a.dz + (size_t)m * a.lddz + 4 * cg));
-            }
-            const int bt = m / a.F_out, f = m - bt * a.F_out;
-            const int b = bt / a.T_out, t = bt - b * a.T_out;
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                if (!kvalid[u]) continue;
-                const int traw = t * a.stride + tapoff[u], fs = f * a.stride_f + tapf[u];
-                int ts = traw;
-                bool ok = fs >= 0 && fs < a.F_in;
-                if (a.pad_mode == VP_PAD_REFLECT) {
-                    ts = ts < 0 ? -ts : ts;
-                    ts = ts >= a.T_in ? 2 * (a.T_in - 1) - ts : ts;
-                } else {
-                    ok = ok && traw >= 0 && traw < a.T_in;
-                }
-                if (!ok) continue;
-                const size_t o = (((size_t)b * a.T_in + ts) * a.F_in + fs) * a.ldx + a.xoff + cc[u];
-                if constexpr (BF) rx[u][r] = *reinterpret_cast<const uint2*>(reinterpret_cast<const bf16_t*>(a.x) + zb * a.xb + o);
-                else rx[u][r] = wg_pack4(*reinterpret_cast<const float4*>(a.x + o));
-            }
-        }
-    };
-    auto put = [&](char* base, int R, int e, const uint2 (&v)[8]) {
-        u16x8 o;
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            const unsigned w = e < 2 ? v[r].x : v[r].y;
-            o[r] = (unsigned short)((e & 1) ? (w >> 16) : (w & 0xffffu));
-        }
-        *reinterpret_cast<u16x8*>(base + R * 128 + ((rg ^ wa_L(R)) << 4)) = o;
-    };
-    auto swrite = [&](int s) {
-        char* dzs = wsm + s * STAGE;
-        char* xs = dzs + 64 * 128;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            if (cg < 16) put(dzs, 4 * cg + e, e, rdz);
-            put(xs, 4 * cg + e, e, rx[0]);
-            put(xs, 128 + 4 * cg + e, e, rx[1]);
-        }
-    };
-    f32x4 acc[4][4];
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc[p][q] = f32x4{0.f, 0.f, 0.f, 0.f};
-    gload(m_begin);
-    int s = 0;
-    for (int mb = m_begin; mb < m_end; mb += WA_RC) {
-        swrite(s);
-        __syncthreads();
-        gload(mb + WA_RC);
-        const char* dzs = wsm + s * STAGE;
-        const char* xs = dzs + 64 * 128;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            bf16x8 af[4], bf[4];
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                const int R = p * 16 + i;
-                af[p] = *reinterpret_cast<const bf16x8*>(dzs + R * 128 + (((ks * 4 + g) ^ wa_L(R)) << 4));
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int R = wv * 64 + q * 16 + i;
-                bf[q] = *reinterpret_cast<const bf16x8*>(xs + R * 128 + (((ks * 4 + g) ^ wa_L(R)) << 4));
-            }
-#pragma unroll
-            for (int p = 0; p < 4; ++p)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[p][q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[p], bf[q], acc[p][q], 0, 0, 0);
-        }
-        s ^= 1;
-    }
-    float* out = a.part + (size_t)blockIdx.z * a.N * a.K;
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int col = kb + wv * 64 + q * 16 + i;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int n = p * 16 + g * 4 + r;
-                if (n < a.N && col < a.K) out[(size_t)n * a.K + col] = acc[p][q][r];
-            }
-        }
-}
-
-// out[i] = sum_k part[k][i]: 16 outputs x 16 partial-lanes per workgroup, fixed order (one thread walking all S partials
-// serially took 33 us per call -- 3.6 ms of a 39 ms training step over ~110 calls)
-// (KW > 1: the weight gradient leaves in the model's (Cout, Cin, KW) layout: partial index (o, tap, c) -> (o, c, tap))
-// (2-D convs, KF > 1: the partial's tap index is kt * KF + kf -- the forward kernel's order -- the model's is kf * KT + kt)
-__device__ __forceinline__ long long oik_index(long long idx, int Cin, int KW, int KF = 1) {
-    if (KW <= 1) return idx;
-    const long long o = idx / ((long long)KW * Cin);
-    const int r = (int)(idx - o * KW * Cin);
-    int j = r / Cin;
-    const int c = r - j * Cin;
-    if (KF > 1) j = (j % KF) * (KW / KF) + j / KF;
-    return (o * Cin + c) * KW + j;
-}
-
-__global__ __launch_bounds__(256) void sum_partials_kernel(const float* part, int S, long long n, float* out, int Cin, int KW, int KF) {
-    __shared__ float sm[16][17];
-    part += (size_t)blockIdx.y * S * n;               // batched weight gradients: one (S, n) slab and one output per blockIdx.y
-    out += (size_t)blockIdx.y * n;
-    const int ol = threadIdx.x & 15, pl = threadIdx.x >> 4;
-    const long long idx = (long long)blockIdx.x * 16 + ol;
-    float s = 0.f;
-    if (idx < n) {
-        int k = pl;
-        for (; k + 48 < S; k += 64) {             // four partial rows per trip, their loads issued together, summed in row order
-            float v[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) v[u] = part[(size_t)(k + 16 * u) * n + idx];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) s += v[u];
-        }
-        for (; k < S; k += 16) s += part[(size_t)k * n + idx];
-    }
-    sm[pl][ol] = s;
-    __syncthreads();
-    if (pl == 0 && idx < n) {
-        float t = 0.f;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) t += sm[k][ol];
-        out[oik_index(idx, Cin, KW, KF)] = t;
-    }
-}
-
-// Many outputs (a weight gradient of >= 32 768 elements): 64 consecutive outputs per workgroup, the S partial rows dealt to the four
-// waves (row k to wave k % 4, four loads in flight per lane) and the four wave sums added in wave order -- a fixed order.  (One thread
-// walking all S rows of its output: 0.97 TB/s on a 33 MB partial slab, 37 us per call and 3-5 % of the 2-D backbones' training steps.)
-__global__ __launch_bounds__(256) void sum_partials_wide_kernel(const float* part, int S, long long n, float* out, int Cin, int KW, int KF) {
-    __shared__ float sm[3][64];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const long long i = (long long)blockIdx.x * 64 + lane;
-    part += (size_t)blockIdx.y * S * n;
-    out += (size_t)blockIdx.y * n;
-    float s = 0.f;
-    if (i < n) {
-        int k = w;
-        for (; k + 12 < S; k += 16) {
-            const float v0 = part[(size_t)k * n + i], v1 = part[(size_t)(k + 4) * n + i];
-            const float v2 = part[(size_t)(k + 8) * n + i], v3 = part[(size_t)(k + 12) * n + i];
-            s += v0; s += v1; s += v2; s += v3;
-        }
-        for (; k < S; k += 4) s += part[(size_t)k * n + i];
-    }
-    if (w) sm[w - 1][lane] = s;
-    __syncthreads();
-    if (w == 0 && i < n) out[oik_index(i, Cin, KW, KF)] = ((s + sm[0][lane]) + sm[1][lane]) + sm[2][lane];
-}
-
+// ---------------------------------------------------------------------------------------------- conv weight layouts
 // wp[o][tap * Cin + c] = w[o][c][tap] (the forward kernel's weight panel) and w2[c][(KW - 1 - tap) * Cout + o] = w[o][c][tap]
 // (the data-gradient conv's: taps reversed, channel roles swapped) from the model's (Cout, Cin, KW) tensor in one launch.
 // 2-D (KF > 1): the model stores (Cout, Cin, KF, KT), tap kf * KT + kt; the kernels' tap order is kt * KF + kf (KW = KF * KT taps).
@@ -948,174 +465,7 @@ int act_kind(int act) {
 
 }  // namespace
 
-static bool getenv_once(const char* name) {       // A/B switches: read at first use (the few names used are distinct call sites)
-    static const bool v = getenv(name) != nullptr;
-    return v;
-}
-
-// many outputs: one thread per output (coalesced over the outputs); few outputs, many partials: 16 x 16 per workgroup
-// (declared in common.h: bn_train.hip reduces its column sums with it)
-void vp_launch_sum_partials(const float* part, int S, long long n, float* out, hipStream_t st, int Cin, int KW, int batch, int KF) {
-    if (n >= 32768) hipLaunchKernelGGL(sum_partials_wide_kernel, dim3((unsigned)((n + 63) / 64), batch), dim3(256), 0, st, part, S, n, out, Cin, KW, KF);
-    else hipLaunchKernelGGL(sum_partials_kernel, dim3((unsigned)((n + 15) / 16), batch), dim3(256), 0, st, part, S, n, out, Cin, KW, KF);
-}
-
 extern "C" {
-
-size_t vp_conv1d_wgrad_workspace_bytes(const vp_conv1d_desc* d) {
-    if (!d || d->Cout <= 0 || d->KW <= 0 || d->Cin <= 0) return 0;
-    const long long M = (long long)d->B * d->T_out * ((d->KF > 1 || d->F_in > 1 || d->F_out > 1) ? d->F_out : 1);
-    const int K = d->KW * d->Cin;
-    const int tiles = ((d->Cout + 63) / 64) * ((K + 63) / 64);
-    int S = 2048 / tiles;
-    if (S < 1) S = 1;
-    if (S > 256) S = 256;
-    if ((long long)S * 64 > M) S = (int)((M + 63) / 64);
-    // the 256-tile kernel of the wide 1x1 layers (wgrad_tr.hip) splits the rows differently
-    if (d->KW == 1 && (d->Cout % 256 == 0 || d->Cout == 128) && (K % 256 == 0 || K == 128) && M >= 32) {
-        const int s2 = vp_wgrad_tr256_splits(M, d->Cout, K);
-        if (s2 > S) S = s2;
-    }
-    return (size_t)S * d->Cout * K * sizeof(float) + 256;
-}
-
-// d: the FORWARD conv's descriptor (x / ldx / xoff and the geometry; w, y, epilogue fields ignored).  dz (B*T_out, lddz) f32.
-static int wgrad_impl(vp_ctx* ctx, const vp_conv1d_desc* d, const float* dz, int lddz, float* dW, void* ws, size_t ws_bytes,
-                      vp_stream stream, bool oik, int nbatch = 1, long long x_bstride = 0, long long dz_bstride = 0) {
-    if (!ctx || !d || !d->x || !dz || !dW) VP_FAIL(ctx, VP_EINVAL, "wgrad: null argument");
-    const bool bf_in = d->dtype_in == VP_BF16;          // x AND dz bf16 in memory (vp_conv1d_wgrad_bf16_oik): bf16 matrix cores only
-    if (d->dtype_in != VP_F32 && !bf_in) VP_FAIL(ctx, VP_EUNSUP, "wgrad: f32 or bf16 tensors");
-    if (d->mfma_bf16 < 0 || d->mfma_bf16 > 3) VP_FAIL(ctx, VP_EINVAL, "wgrad: mfma_bf16 %d outside 0..3", d->mfma_bf16);
-    const bool two_d = d->KF > 1 || d->F_in > 1 || d->F_out > 1;
-    if (two_d && (d->KF < 1 || d->KW % d->KF || d->F_in < 1 || d->F_out < 1 || d->stride_f < 1 || d->pad_mode != VP_PAD_ZERO))
-        VP_FAIL(ctx, VP_EINVAL, "wgrad: bad 2-D geometry (zero padding only)");
-    if (d->B <= 0 || d->T_in <= 0 || d->T_out <= 0 || d->Cin <= 0 || d->Cout <= 0 || d->KW <= 0 || d->stride <= 0 || d->dilation <= 0)
-        VP_FAIL(ctx, VP_EINVAL, "wgrad: bad shape");
-    const size_t need = vp_conv1d_wgrad_workspace_bytes(d) * (size_t)nbatch;
-    if (!ws || ws_bytes < need) VP_FAIL(ctx, VP_EWORKSPACE, "wgrad: workspace %zu < %zu", ws_bytes, need);
-    if (nbatch < 1 || (nbatch > 1 && !(d->dtype_in == VP_BF16))) VP_FAIL(ctx, VP_EINVAL, "wgrad: batched launches take bf16 operands");
-    const long long M = (long long)d->B * d->T_out * (two_d ? d->F_out : 1);
-    if (M > 0x7fffffffLL / 2) VP_FAIL(ctx, VP_EINVAL, "wgrad: too many rows");
-    const int K = d->KW * d->Cin;
-    const int tn = (d->Cout + 63) / 64, tk = (K + 63) / 64;
-    int S = 2048 / (tn * tk);
-    if (S < 1) S = 1;
-    if (S > 256) S = 256;
-    if (nbatch > 1 && S > 512 / nbatch) S = 512 / nbatch > 1 ? 512 / nbatch : 1;      // the batch fills the chip: fewer, longer row splits (less to reduce)
-    if ((long long)S * 64 > M) S = (int)((M + 63) / 64);
-    // split precision (f32 operands): the 128 x 128 kernel, one workgroup per CU.  Mode 3 (pre-split forward weights) is mode 2 here:
-    // the weights are not an operand of their own gradient
-    const bool x3 = (d->mfma_bf16 == 2 || d->mfma_bf16 == 3) && !bf_in;
-    if ((d->mfma_bf16 || bf_in) && nbatch == 1) {
-        // The 128 x 128 mixed-precision kernel keeps two workgroups per CU resident.  A grid of 1.5 rounds of them costs two rounds of
-        // time with half-empty CUs in the second (a 3 x 3 conv of 32 channels: 3 tiles x 256 splits = 768 workgroups on 512 slots): take the
-        // largest split count that fills WHOLE rounds instead (3 x 170 = 510: the same rows in one round, and a third fewer partial rows).
-        static int cus_dev[64] = {};
-        int& cus = cus_dev[ctx->device & 63];
-        if (!cus && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess) cus = 256;
-        const long long slots = (x3 ? 1LL : 2LL) * cus;
-        const long long tiles128 = (long long)((K + 127) / 128) * ((d->Cout + 127) / 128);
-        const long long W = tiles128 * S;
-        if (W > slots) {
-            const long long S2 = slots * (W / slots) / tiles128;
-            if (S2 >= 1 && S2 < S) S = (int)S2;
-        }
-    }
-    if ((d->Cin | d->Cout | d->ldx | d->xoff | lddz) & 3) VP_FAIL(ctx, VP_EINVAL, "wgrad: Cin / Cout / ldx / xoff / lddz must be multiples of 4");
-    int rps = (int)((M + S - 1) / S);
-    const int rq = (d->mfma_bf16 || bf_in) ? 64 : 32;             // rows per staged chunk of the kernel
-    rps = (rps + rq - 1) / rq * rq;
-    S = (int)((M + rps - 1) / rps);
-    WgradArgs a;
-    a.x = (const float*)d->x; a.dz = dz; a.part = (float*)ws;
-    a.ldx = d->ldx; a.xoff = d->xoff; a.lddz = lddz; a.M = (int)M; a.N = d->Cout; a.K = K; a.Cin = d->Cin;
-    a.T_in = d->T_in; a.T_out = d->T_out; a.dilation = d->dilation; a.stride = d->stride; a.pad_left = d->pad_left;
-    a.pad_mode = d->pad_mode; a.rows_per_split = rps;
-    a.F_in = two_d ? d->F_in : 1; a.F_out = two_d ? d->F_out : 1; a.KF = two_d ? d->KF : 1;
-    a.stride_f = two_d ? d->stride_f : 1; a.pad_f = two_d ? d->pad_f : 0;
-    a.splits = S; a.xb = x_bstride; a.dzb = dz_bstride;
-    hipStream_t st = (hipStream_t)stream;
-    static const bool no_tr256 = getenv("VPMI_WGRAD_TR256_OFF") != nullptr;      // A/B switch (tools/train_probe.py)
-    const bool simple = K == d->Cin && d->stride == 1 && d->pad_left == 0 && d->T_in == d->T_out && !two_d;
-    int tr = VP_EUNSUP;
-    if (bf_in && simple && nbatch == 1 && !no_tr256) {
-        int s2 = 0;
-        tr = vp_wgrad_tr256_bf16(ctx, d->x, d->ldx, d->xoff, dz, lddz, M, d->Cout, K, (float*)ws, &s2, st);
-        if (tr == VP_OK) S = s2;
-        else if (tr != VP_EUNSUP) return tr;
-    }
-    if (tr == VP_OK) {
-    } else if (d->mfma_bf16 || bf_in) {
-        constexpr int smem = 2 * 2 * WA_T * 128;
-        static bool attr_dev[64] = {};                    // the attribute is per DEVICE (a process may drive several GPUs)
-    bool& attr_set = attr_dev[ctx->device & 63];
-        if (!attr_set) {
-            VP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_amp_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-            VP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_amp_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-            attr_set = true;
-        }
-        const dim3 grid((K + WA_T - 1) / WA_T, (d->Cout + WA_T - 1) / WA_T, S * nbatch);
-        // narrow layer with bf16 operands in memory (the batched Res2Net chunk convs): its own tile shape.  The f32-operand flavour of the
-        // kernel (2-D taps too: the 32- / 64-channel convs of ResNetSE / ERes2Net / the FCM head) is built but NOT dispatched: measured
-        // slower than the square tile there (ResNetSE step 22.7 -> 23.8 ms, ERes2Net 31.4 -> 33.9 ms, CAM++ 30.1 -> 31.8 ms;
-        // VPMI_WGRAD_NARROW_F32=1 dispatches it for study)
-        if (!x3 && d->Cout <= 64 && K > 128 && ((bf_in && !two_d && d->stride == 1) || (!bf_in && getenv_once("VPMI_WGRAD_NARROW_F32")))) {
-            constexpr int smem64 = 2 * (64 + 256) * 128;
-            static bool attr64_dev[64] = {};
-            bool& attr64 = attr64_dev[ctx->device & 63];
-            if (!attr64) {
-                VP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_n64_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, smem64));
-                VP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_n64_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, smem64));
-                attr64 = true;
-            }
-            const dim3 g64((K + 255) / 256, 1, S * nbatch);
-            if (bf_in) hipLaunchKernelGGL(conv_wgrad_n64_kernel<true>, g64, dim3(256), smem64, st, a);
-            else hipLaunchKernelGGL(conv_wgrad_n64_kernel<false>, g64, dim3(256), smem64, st, a);
-        } else if (bf_in) hipLaunchKernelGGL(conv_wgrad_amp_kernel<true>, grid, dim3(256), smem, st, a);
-        else if (x3) {
-            static bool attr3_dev[64] = {};
-            bool& attr3 = attr3_dev[ctx->device & 63];
-            if (!attr3) {
-                VP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_amp_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * smem));
-                attr3 = true;
-            }
-            hipLaunchKernelGGL((conv_wgrad_amp_kernel<false, true>), grid, dim3(256), 2 * smem, st, a);
-        } else hipLaunchKernelGGL(conv_wgrad_amp_kernel<false>, grid, dim3(256), smem, st, a);
-    } else {
-        hipLaunchKernelGGL(conv_wgrad_kernel, dim3(tk, tn, S), dim3(256), 0, st, a);
-    }
-    VP_LAUNCH_CHECK(ctx, "conv_wgrad");
-    const long long n = (long long)d->Cout * K;
-    vp_launch_sum_partials((const float*)ws, S, n, dW, st, d->Cin, oik ? d->KW : 1, nbatch, (oik && two_d) ? d->KF : 1);
-    VP_LAUNCH_CHECK(ctx, "wgrad_reduce");
-    return VP_OK;
-}
-
-int vp_conv1d_wgrad_f32(vp_ctx* ctx, const vp_conv1d_desc* d, const float* dz, int lddz, float* dW, void* ws, size_t ws_bytes,
-                        vp_stream stream) {
-    return wgrad_impl(ctx, d, dz, lddz, dW, ws, ws_bytes, stream, false);
-}
-
-// the same gradient in the model's own (Cout, Cin, KW) layout (KW = KT * KF taps for the 2-D convs): no permute copy afterwards
-int vp_conv1d_wgrad_oik_f32(vp_ctx* ctx, const vp_conv1d_desc* d, const float* dz, int lddz, float* dW, void* ws, size_t ws_bytes,
-                            vp_stream stream) {
-    return wgrad_impl(ctx, d, dz, lddz, dW, ws, ws_bytes, stream, true);
-}
-
-// x (d->x, d->dtype_in == VP_BF16) and dz both bf16 in memory; dW f32 in the model's (Cout, Cin, KW) layout
-int vp_conv1d_wgrad_bf16_oik(vp_ctx* ctx, const vp_conv1d_desc* d, const void* dz, int lddz, float* dW, void* ws, size_t ws_bytes,
-                             vp_stream stream) {
-    if (!d || d->dtype_in != VP_BF16) VP_FAIL(ctx, VP_EINVAL, "wgrad_bf16: the descriptor's dtype_in must be bf16");
-    return wgrad_impl(ctx, d, (const float*)dz, lddz, dW, ws, ws_bytes, stream, true);
-}
-
-// nbatch convs of identical geometry in ONE launch: conv c reads x + c * x_bstride and dz + c * dz_bstride (bf16 elements) and writes
-// dW + c * Cout * Cin * KW; ws = nbatch x vp_conv1d_wgrad_workspace_bytes(d).  (The seven chunk convs of a Res2Net block.)
-int vp_conv1d_wgrad_bf16_oik_batched(vp_ctx* ctx, const vp_conv1d_desc* d, const void* dz, int lddz, float* dW, int nbatch, long long x_bstride,
-                                     long long dz_bstride, void* ws, size_t ws_bytes, vp_stream stream) {
-    if (!d || d->dtype_in != VP_BF16) VP_FAIL(ctx, VP_EINVAL, "wgrad_bf16: the descriptor's dtype_in must be bf16");
-    return wgrad_impl(ctx, d, (const float*)dz, lddz, dW, ws, ws_bytes, stream, true, nbatch, x_bstride, dz_bstride);
-}
 
 int vp_conv_weight_layouts_f32(vp_ctx* ctx, const float* w, int Cout, int Cin, int KW, float* wp, float* w2, vp_stream stream) {
     if (!ctx || !w || (!wp && !w2) || Cout <= 0 || Cin <= 0 || KW <= 0) VP_FAIL(ctx, VP_EINVAL, "weight_layouts: bad arguments");

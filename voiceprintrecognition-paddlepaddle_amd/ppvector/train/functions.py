@@ -81,6 +81,24 @@ def _conv_desc(x, B, T_in, T_out, Cin, Cout, KW, dil, pad_mode, pad_left, w, bia
     return d
 
 
+def _wgrad(d, dz, lddz, dW, nbatch=1, x_bstride=0, dz_bstride=0):
+    """The weight gradient of the forward conv `d` into dW (f32, the model's (Cout, Cin, KW) / (Cout, Cin, KF, KT) layout): every
+    call of csrc/wgrad.hip is made here (kernel families and workspace contract: docs/wgrad.md).  d.dtype_in says what d.x and dz
+    hold in memory -- f32, or bf16 for both -- and is set before the call; nbatch > 1 (bf16 only): conv c reads d.x + c * x_bstride and
+    dz + c * dz_bstride elements and writes dW[c].  Allocates the workspace (nbatch x the query, which reads the geometry only) and
+    launches on the current stream."""
+    lib, hctx = N.lib(), N.ctx(dW.device)
+    ws = _bytes(lib.vp_conv1d_wgrad_workspace_bytes(C.byref(d)) * nbatch, dW.device)
+    tail = (ws.data_ptr(), ws.numel(), N.stream_ptr())
+    if nbatch > 1:
+        rc = lib.vp_conv1d_wgrad_bf16_oik_batched(hctx, C.byref(d), dz.data_ptr(), lddz, dW.data_ptr(), nbatch, x_bstride, dz_bstride, *tail)
+    elif d.dtype_in == N.VP_BF16:
+        rc = lib.vp_conv1d_wgrad_bf16_oik(hctx, C.byref(d), dz.data_ptr(), lddz, dW.data_ptr(), *tail)
+    else:
+        rc = lib.vp_conv1d_wgrad_oik_f32(hctx, C.byref(d), dz.data_ptr(), lddz, dW.data_ptr(), *tail)
+    _chk(rc, hctx)
+
+
 def _act_bwd(act, dy, y):
     """-> d(input) of the activation `act` (VP_ACT_*) from its output gradient dy and the tensor y its backward reads (f32, same shape)"""
     lib, hctx = N.lib(), N.ctx(dy.device)
@@ -546,14 +564,9 @@ def _conv_block_bwd(ctx, dy, skip=None, fold=None, utt=None):
     # weight gradient
     d = _conv_desc(x, B, T_in, T_out, Cin, Cout, KW, dil, _PAD[pad], pad_left, weight)
     dW = torch.empty((Cout, Cin, KW), dtype=torch.float32, device=dev)      # reduced straight into the model's layout
-    ws = _bytes(lib.vp_conv1d_wgrad_workspace_bytes(C.byref(d)), dev)
     if wide:                                            # x (saved as bf16) and dz both bf16 in memory
         d.dtype_in = N.VP_BF16
-        _chk(lib.vp_conv1d_wgrad_bf16_oik(hctx, C.byref(d), dz.data_ptr(), Cout, dW.data_ptr(), ws.data_ptr(), ws.numel(),
-                                          N.stream_ptr()), hctx)
-    else:
-        _chk(lib.vp_conv1d_wgrad_oik_f32(hctx, C.byref(d), dz.data_ptr(), Cout, dW.data_ptr(), ws.data_ptr(), ws.numel(),
-                                         N.stream_ptr()), hctx)
+    _wgrad(d, dz, Cout, dW)
     # data gradient: the forward kernel over dz with reversed taps and swapped channel roles
     dx = None
     if ctx.needs_input_grad[0]:
@@ -841,10 +854,8 @@ class Res2Fn(torch.autograd.Function):
             wd.dtype_in = wd.dtype_out = N.VP_BF16
             wd.B, wd.T_in, wd.T_out, wd.Cin, wd.Cout, wd.KW, wd.dilation, wd.stride = B, T, T, 64, 64, 3, cfg['dilation'], 1
             wd.pad_mode, wd.pad_left, wd.ldx, wd.xoff, wd.ldy, wd.mfma_bf16 = N.VP_PAD_REFLECT, cfg['dilation'], 64, 0, 64, 1
-            wws = _bytes(lib.vp_conv1d_wgrad_workspace_bytes(C.byref(wd)) * (S - 1), dout.device)
             wd.x, wd.w = inb.data_ptr(), wg[0].data_ptr()                # weight gradients dz_i^T in_i of all chunks in one launch
-            _chk(lib.vp_conv1d_wgrad_bf16_oik_batched(hctx, C.byref(wd), dzb.data_ptr(), 64, dw_all.data_ptr(), S - 1, M * 64, M * 64,
-                                                      wws.data_ptr(), wws.numel(), N.stream_ptr()), hctx)
+            _wgrad(wd, dzb, 64, dw_all, nbatch=S - 1, x_bstride=M * 64, dz_bstride=M * 64)
             for i in range(S - 1):
                 grads[6 * i:6 * i + 4] = [dw_all[i], dvec[i, 0], dvec[i, 1], dvec[i, 2]]
             return (dx, None, *grads)
@@ -1618,8 +1629,7 @@ class Conv2dBlock(torch.autograd.Function):
         d = _conv_desc(x, B, T, To, Cin, Cout, KT * KF, dil, N.VP_PAD_ZERO, pad, weight)
         d.F_in, d.F_out, d.KF, d.stride, d.stride_f, d.pad_f = Fq, Fo, KF, st, sf, padf
         dW = torch.empty((Cout, Cin, KF, KT), dtype=torch.float32, device=dev)       # reduced straight into the model's layout
-        ws = _bytes(lib.vp_conv1d_wgrad_workspace_bytes(C.byref(d)), dev)
-        _chk(lib.vp_conv1d_wgrad_oik_f32(hctx, C.byref(d), dz.data_ptr(), Cout, dW.data_ptr(), ws.data_ptr(), ws.numel(), N.stream_ptr()), hctx)
+        _wgrad(d, dz, Cout, dW)
         dx = None
         if ctx.needs_input_grad[0]:
             src = dz
