@@ -5,6 +5,8 @@
  * has NO FFI / operator-plugin interface: its seams are Python call signatures into PaddlePaddle
  * (SURVEY.md section 8(b)).  Each entry point below therefore names the reference Python call site whose
  * arithmetic it replaces; INTEGRATION.md shows the ctypes binding a ppvector maintainer would add.
+ * A few entry points do something the reference does not do at all (adaptive score normalisation at the end of this file); their
+ * comments say "no reference call site: an extension" instead.
  *
  * Conventions
  *   - every pointer is a DEVICE pointer unless the name ends in _h; the caller (PyTorch) owns all
@@ -1128,6 +1130,48 @@ int vp_trial_ranks_counts_f32(vp_ctx* ctx, const int* trial_labels, int Nt, cons
 int vp_trial_ranks_select_f32(vp_ctx* ctx, const int* trial_labels, int Nt, const int* enroll_labels, int Ne, int D, long long NT,
                               float lo, float hi, int level, long long prefix, long long* digits, const void* ws, size_t ws_bytes,
                               vp_stream stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Adaptive score normalisation, AS-norm (csrc/cohort_stats.hip, csrc/score_norm.h, docs/score_norm.md).  No reference call site: an
+ * extension -- the reference reports raw-cosine EER / minDCF only.  A cohort is C embeddings (C, D).  For an embedding x, with
+ * N = min(top_n, C) and T the N largest of its C cosines against the cohort (cosines by the contract of the trial scorer above:
+ * unit rows with the length in float64, one k-ordered fma chain), mean = sum T / N and std = sqrt(max(sum T^2 / N - mean^2, 0)),
+ * evaluated in float64 on the f32 cosines without contraction and rounded once each; r = 1 / max(std, 1e-6f) in f32; the normalised
+ * score of a trial t against an enrolment e with cosine s is z = 0.5f ((s - mean_e) r_e + (s - mean_t) r_t), six f32 operations
+ * each rounded on its own, in that order.  One device function computes z for every kernel below, so a pair gets the same z wherever
+ * it is computed.
+ * vp_cohort_stats_f32 -- no reference call site: an extension.  x (Q, D) and cohort (C, D) are raw rows; the cohort's unit rows go
+ *   to the workspace (C D floats), and one workgroup per 32 rows of x walks them once per digit of a radix selection of the N-th
+ *   largest cosine (8-bit digits, 7-bit for D >= 1020; per-column histograms in LDS) and once more for the two sums: nothing of size
+ *   Q C is written, ties at the N-th place need no rule.  mean, std (Q) f32.  Integer counts and fixed-order float64 sums: no float
+ *   atomics, no grid barrier; two runs give the same bits.  Q, C, top_n >= 1, D % 4 == 0, D <= 1024, 16-byte aligned rows;
+ *   anything else: the workspace query returns 0 and the entry point VP_EUNSUP (checked before anything touches a device).  Null
+ *   pointer: VP_EINVAL.  Workspace too small: VP_EWORKSPACE.
+ * vp_score_norm_recip_f32 -- no reference call site: an extension.  r[i] = 1 / max(std[i], 1e-6f), correctly rounded; n >= 1.
+ * vp_score_norm_apply_f32 -- no reference call site: an extension.  scores (Nt, Ne) cosines -> z in place, from the trials' and the
+ *   enrolments' mean and r (Nt and Ne floats each).  Nt, Ne >= 1, else VP_EUNSUP.
+ * vp_trial_ranks_targets_norm_f32 / _counts_norm_f32 / _select_norm_f32 -- no reference call site: an extension.  The three passes
+ *   of the trial scorer above with z in the place of the cosine: the same arguments, shapes, workspace and errors, and four more
+ *   arrays, the trials' mean and r (Nt) and the enrolments' mean and r (Ne).  targets, sorted_targets, lo and hi are z values.
+ * ---------------------------------------------------------------------------------------------- */
+size_t vp_cohort_stats_workspace_bytes(int Q, int C, int D);
+int vp_cohort_stats_f32(vp_ctx* ctx, const float* x, int Q, const float* cohort, int C, int D, int top_n, float* mean, float* std,
+                        void* ws, size_t ws_bytes, vp_stream stream);
+int vp_score_norm_recip_f32(vp_ctx* ctx, const float* std, long long n, float* r, vp_stream stream);
+int vp_score_norm_apply_f32(vp_ctx* ctx, float* scores, int Nt, int Ne, const float* trial_mean, const float* trial_r,
+                            const float* enroll_mean, const float* enroll_r, vp_stream stream);
+int vp_trial_ranks_targets_norm_f32(vp_ctx* ctx, const float* trials, const int* trial_labels, const long long* trial_offsets, int Nt,
+                                    const float* enroll, const int* enroll_labels, const int* enroll_ranks, int Ne, int D,
+                                    long long NT, float* targets, const float* trial_mean, const float* trial_r,
+                                    const float* enroll_mean, const float* enroll_r, void* ws, size_t ws_bytes, vp_stream stream);
+int vp_trial_ranks_counts_norm_f32(vp_ctx* ctx, const int* trial_labels, int Nt, const int* enroll_labels, int Ne, int D,
+                                   const float* sorted_targets, long long NT, long long* hist, const float* trial_mean,
+                                   const float* trial_r, const float* enroll_mean, const float* enroll_r, const void* ws,
+                                   size_t ws_bytes, vp_stream stream);
+int vp_trial_ranks_select_norm_f32(vp_ctx* ctx, const int* trial_labels, int Nt, const int* enroll_labels, int Ne, int D,
+                                   long long NT, float lo, float hi, int level, long long prefix, long long* digits,
+                                   const float* trial_mean, const float* trial_r, const float* enroll_mean, const float* enroll_r,
+                                   const void* ws, size_t ws_bytes, vp_stream stream);
 
 #ifdef __cplusplus
 }

@@ -1,4 +1,5 @@
-// The cosine tile walk of gallery.hip (gallery_score_kernel) and trial_ranks.hip (trial_pass_kernel<MODE>): device code, included by both.
+// The cosine tile walk of gallery.hip (gallery_score_kernel), trial_ranks.hip (trial_pass_kernel<MODE, NORM>) and cohort_stats.hip
+// (cohort_stats_kernel): device code, included by all three.
 //
 // A workgroup of 256 threads holds a tile of 32 unit rows ("columns": queries, trials) in LDS as [k][column], the B operand of
 // v_mfma_f32_32x32x2_f32, and walks `slabs_per_wg` slabs of SLAB = 128 rows of a unit row matrix.  Each of its four waves owns 32 rows of
@@ -33,6 +34,17 @@ __device__ __forceinline__ double sum_sq(float4 v) { return (double)v.x * v.x + 
 __device__ __forceinline__ double inv_length(double ss) { return ss > 0.0 ? 1.0 / sqrt(ss) : 0.0; }
 __device__ __forceinline__ float4 scale4(float4 v, double inv) {
     return make_float4((float)(v.x * inv), (float)(v.y * inv), (float)(v.z * inv), (float)(v.w * inv));
+}
+
+// One row -> its unit row, by one wave (lane = 0 .. 63): 16-byte loads, the sum of squares added across the wave's lanes.  The
+// unit_rows_kernel of trial_ranks.hip and of cohort_stats.hip are a wave per row around it.
+__device__ __forceinline__ void unit_row(const float* __restrict__ src, float* __restrict__ dst, int D, int lane) {
+    double ss = 0.0;
+    for (int k = lane * 4; k < D; k += 256) ss += sum_sq(*reinterpret_cast<const float4*>(src + k));
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
+    const double inv = inv_length(ss);
+    for (int k = lane * 4; k < D; k += 256) *reinterpret_cast<float4*>(dst + k) = scale4(*reinterpret_cast<const float4*>(src + k), inv);
 }
 
 // Rows first .. first + 31 of x (n rows of D floats) -> qs [Dp][32], Dp = D rounded up to 8: eight threads per column, 16-byte loads;

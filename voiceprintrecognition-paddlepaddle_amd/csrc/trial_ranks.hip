@@ -2,7 +2,7 @@
 // target scores and, for every gap between two of them, HOW MANY non-target scores fall into it.  docs/trial_ranks.md has the method.
 //
 // vp_trial_ranks_targets_f32  unit_rows_kernel writes both sides as unit rows into the workspace (a wave per row); then the targets pass.
-// trial_pass_kernel<MODE>     a workgroup holds 32 unit trial rows in LDS and walks `slabs_per_wg` slabs of enrol rows with cos_tile.h's
+// trial_pass_kernel<MODE, NORM>  a workgroup holds 32 unit trial rows in LDS and walks `slabs_per_wg` slabs of enrol rows with cos_tile.h's
 //                             walk, which states how a score is summed and why a pair has the same bits in every pass.
 //                             The passes differ in what a lane does with its 16 scores:
 //   TARGETS  a pair with equal labels writes its score to targets[trial_offset[i] + enroll_rank[j]]: a place the labels alone fix.
@@ -13,7 +13,10 @@
 //   SELECT   a pair with different labels and lo < s <= hi whose order-preserving key agrees with `prefix` above the digit in hand
 //            counts that digit (11, 11 and 10 bits: an LDS histogram of 2048 counters; 65 536 would not fit beside the tile).
 // Integer counts only: no float atomics, no grid barrier, no spinning; the result does not depend on arrival order.
+// NORM: the score every pass works on is score_norm.h's z of the cosine (adaptive score normalisation, docs/score_norm.md) -- the
+// vp_trial_ranks_*_norm_f32 entry points; NORM = false is the cosine itself.
 #include "cos_tile.h"
+#include "score_norm.h"
 
 namespace {
 
@@ -76,15 +79,7 @@ __global__ __launch_bounds__(256) void unit_rows_kernel(const float* __restrict_
     const int lane = threadIdx.x & 63;
     const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= rows) return;              // wave-uniform
-    const float* src = x + (size_t)r * D;
-    float* dst = y + (size_t)r * D;
-    double ss = 0.0;
-    for (int k = lane * 4; k < D; k += 256) ss += cos_tile::sum_sq(*reinterpret_cast<const float4*>(src + k));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
-    const double inv = cos_tile::inv_length(ss);
-    for (int k = lane * 4; k < D; k += 256)
-        *reinterpret_cast<float4*>(dst + k) = cos_tile::scale4(*reinterpret_cast<const float4*>(src + k), inv);
+    cos_tile::unit_row(x + (size_t)r * D, y + (size_t)r * D, D, lane);
 }
 
 // ------------------------------------------------------------------------------------------------ the passes
@@ -109,6 +104,11 @@ struct PassArgs {
     unsigned digit_mask;
     // COUNTS: (NT + 1) bins; SELECT: DIGIT_BINS
     unsigned long long* hist;
+    // NORM: per trial and per enrol row the mean of its top cohort scores and r = 1 / max(std, floor)
+    const float* tmean;
+    const float* tr;
+    const float* emean;
+    const float* er;
 };
 
 // #{i < n : a[i] < s}, a ascending
@@ -122,7 +122,7 @@ __device__ __forceinline__ int count_below(const float* a, int n, float s) {
 }
 
 // grid (trial tiles, row ranges), 256 threads, dynamic LDS: qs [Dp][32] | COUNTS: pivots [P], counts [H] | SELECT: counts [DIGIT_BINS]
-template <int MODE>
+template <int MODE, bool NORM>
 __global__ __launch_bounds__(256) void trial_pass_kernel(const PassArgs a) {
     extern __shared__ __align__(16) float smem[];
     const int D = a.D, Dp = (D + 7) & ~7;
@@ -144,6 +144,8 @@ __global__ __launch_bounds__(256) void trial_pass_kernel(const PassArgs a) {
     const int lq = my_q ? a.tl[q] : 0;
     long long off = 0;
     if (MODE == TARGETS && my_q) off = a.toff[q];
+    float mt = 0.f, rt = 0.f;
+    if (NORM && my_q) { mt = a.tmean[q]; rt = a.tr[q]; }
     cos_tile::walk<long long>(qs, a.eu, a.Ne, D, range, a.slabs_per_wg, [&](long long r0, const cos_tile::f32x16& acc) {
         const long long rb = r0 + 4 * half;
 #pragma unroll
@@ -151,7 +153,7 @@ __global__ __launch_bounds__(256) void trial_pass_kernel(const PassArgs a) {
             const long long r = rb + 8 * (v >> 2) + (v & 3);
             if (!my_q || r >= a.Ne) continue;
             const bool same = a.el[r] == lq;
-            const float s = acc[v];
+            const float s = NORM ? score_norm::z(acc[v], a.emean[r], a.er[r], mt, rt) : acc[v];
             if (MODE == TARGETS) {
                 if (!same) continue;
                 const long long at = off + a.erank[r];
@@ -183,22 +185,40 @@ __global__ __launch_bounds__(256) void trial_pass_kernel(const PassArgs a) {
     }
 }
 
-template <int MODE>
-int launch(vp_ctx* ctx, const PassArgs& a, const Plan& p, size_t lds, hipStream_t st, const char* name) {
+template <int MODE, bool NORM>
+int launch_as(vp_ctx* ctx, const PassArgs& a, const Plan& p, size_t lds, hipStream_t st, const char* name) {
     static bool attr_dev[64] = {};              // the attribute is per device (and per instantiation)
     bool& attr_set = attr_dev[ctx->device & 63];
     if (!attr_set) {
-        VP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(trial_pass_kernel<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        MAX_LDS));
+        VP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(trial_pass_kernel<MODE, NORM>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS));
         attr_set = true;
     }
-    hipLaunchKernelGGL(trial_pass_kernel<MODE>, dim3(p.qtiles, p.ranges), dim3(256), lds, st, a);
+    hipLaunchKernelGGL((trial_pass_kernel<MODE, NORM>), dim3(p.qtiles, p.ranges), dim3(256), lds, st, a);
     VP_LAUNCH_CHECK(ctx, name);
     return VP_OK;
 }
 
-PassArgs common_args(const Plan& p, const void* ws, const int* tl, int Nt, const int* el, int Ne, int D, long long NT) {
+// a.tmean set: the normalised pass
+template <int MODE>
+int launch(vp_ctx* ctx, const PassArgs& a, const Plan& p, size_t lds, hipStream_t st, const char* name) {
+    return a.tmean ? launch_as<MODE, true>(ctx, a, p, lds, st, name) : launch_as<MODE, false>(ctx, a, p, lds, st, name);
+}
+
+// The four statistics arrays of a vp_trial_ranks_*_norm_f32 call; nullptr: the plain entry point.
+struct Norm {
+    const float *tmean, *tr, *emean, *er;
+    bool complete() const { return tmean && tr && emean && er; }
+};
+
+PassArgs common_args(const Plan& p, const void* ws, const int* tl, int Nt, const int* el, int Ne, int D, long long NT, const Norm* nz) {
     PassArgs a{};
+    if (nz) {
+        a.tmean = nz->tmean;
+        a.tr = nz->tr;
+        a.emean = nz->emean;
+        a.er = nz->er;
+    }
     a.tu = (const float*)ws;
     a.eu = (const float*)((const char*)ws + p.unit_t);
     a.tl = tl;
@@ -212,7 +232,72 @@ PassArgs common_args(const Plan& p, const void* ws, const int* tl, int Nt, const
 }
 
 #define TRIAL_UNSUP(ctx, what) \
-    VP_FAIL(ctx, VP_EUNSUP, what ": Nt, Ne >= 1, D %% 4 == 0, D <= %d, 1 <= NT <= %lld", MAX_D, MAX_NT)
+    VP_FAIL(ctx, VP_EUNSUP, "%s: Nt, Ne >= 1, D %% 4 == 0, D <= %d, 1 <= NT <= %lld", what, MAX_D, MAX_NT)
+
+// The three passes; nz = nullptr: on the cosines (vp_trial_ranks_*_f32), else on z (vp_trial_ranks_*_norm_f32).
+int targets_pass(vp_ctx* ctx, const char* what, const float* trials, const int* trial_labels, const long long* trial_offsets, int Nt,
+                 const float* enroll, const int* enroll_labels, const int* enroll_ranks, int Ne, int D, long long NT, float* targets,
+                 const Norm* nz, void* ws, size_t ws_bytes, vp_stream stream) {
+    if (!supported(Nt, Ne, D, NT)) TRIAL_UNSUP(ctx, what);       // first, and without a context: needs no device
+    if (!ctx || !trials || !trial_labels || !trial_offsets || !enroll || !enroll_labels || !enroll_ranks || !targets || !ws ||
+        (nz && !nz->complete()))
+        VP_FAIL(ctx, VP_EINVAL, "%s: null pointer", what);
+    const Plan p = plan(Nt, Ne, D, NT);
+    if (ws_bytes < p.bytes) VP_FAIL(ctx, VP_EWORKSPACE, "%s: workspace %zu < %zu bytes", what, ws_bytes, p.bytes);
+    hipStream_t st = (hipStream_t)stream;
+    PassArgs a = common_args(p, ws, trial_labels, Nt, enroll_labels, Ne, D, NT, nz);
+    hipLaunchKernelGGL(unit_rows_kernel, dim3((Nt + 3) / 4), dim3(256), 0, st, trials, (long long)Nt, D, (float*)ws);
+    VP_LAUNCH_CHECK(ctx, "unit_rows_kernel");
+    hipLaunchKernelGGL(unit_rows_kernel, dim3((Ne + 3) / 4), dim3(256), 0, st, enroll, (long long)Ne, D, (float*)((char*)ws + p.unit_t));
+    VP_LAUNCH_CHECK(ctx, "unit_rows_kernel");
+    a.toff = trial_offsets;
+    a.erank = enroll_ranks;
+    a.targets = targets;
+    return launch<TARGETS>(ctx, a, p, p.tile_lds, st, "trial_pass_kernel<targets>");
+}
+
+int counts_pass(vp_ctx* ctx, const char* what, const int* trial_labels, int Nt, const int* enroll_labels, int Ne, int D,
+                const float* sorted_targets, long long NT, long long* hist, const Norm* nz, const void* ws, size_t ws_bytes,
+                vp_stream stream) {
+    if (!supported(Nt, Ne, D, NT)) TRIAL_UNSUP(ctx, what);
+    if (!ctx || !trial_labels || !enroll_labels || !sorted_targets || !hist || !ws || (nz && !nz->complete()))
+        VP_FAIL(ctx, VP_EINVAL, "%s: null pointer", what);
+    const Plan p = plan(Nt, Ne, D, NT);
+    if (ws_bytes < p.bytes) VP_FAIL(ctx, VP_EWORKSPACE, "%s: workspace %zu < %zu bytes", what, ws_bytes, p.bytes);
+    hipStream_t st = (hipStream_t)stream;
+    PassArgs a = common_args(p, ws, trial_labels, Nt, enroll_labels, Ne, D, NT, nz);
+    a.st = sorted_targets;
+    a.P = p.P;
+    a.stride = p.stride;
+    a.H = p.H;
+    a.hist = reinterpret_cast<unsigned long long*>(hist);
+    VP_HIP(ctx, hipMemsetAsync(hist, 0, (size_t)(NT + 1) * 8, st));
+    return launch<COUNTS>(ctx, a, p, p.count_lds, st, "trial_pass_kernel<counts>");
+}
+
+int select_pass(vp_ctx* ctx, const char* what, const int* trial_labels, int Nt, const int* enroll_labels, int Ne, int D, long long NT,
+                float lo, float hi, int level, long long prefix, long long* digits, const Norm* nz, const void* ws, size_t ws_bytes,
+                vp_stream stream) {
+    if (!supported(Nt, Ne, D, NT)) TRIAL_UNSUP(ctx, what);
+    if (!ctx || !trial_labels || !enroll_labels || !digits || !ws || (nz && !nz->complete()))
+        VP_FAIL(ctx, VP_EINVAL, "%s: null pointer", what);
+    if (level < 0 || level > 2 || prefix < 0 || prefix > 0xffffffffLL) VP_FAIL(ctx, VP_EINVAL, "%s: level, prefix", what);
+    const Plan p = plan(Nt, Ne, D, NT);
+    if (ws_bytes < p.bytes) VP_FAIL(ctx, VP_EWORKSPACE, "%s: workspace %zu < %zu bytes", what, ws_bytes, p.bytes);
+    hipStream_t st = (hipStream_t)stream;
+    PassArgs a = common_args(p, ws, trial_labels, Nt, enroll_labels, Ne, D, NT, nz);
+    static const int shifts[3] = {21, 10, 0};
+    static const unsigned masks[3] = {0u, 0xffe00000u, 0xfffffc00u}, digit_masks[3] = {2047u, 2047u, 1023u};
+    a.lo = lo;
+    a.hi = hi;
+    a.shift = shifts[level];
+    a.prefix_mask = masks[level];
+    a.prefix = (unsigned)prefix & masks[level];
+    a.digit_mask = digit_masks[level];
+    a.hist = reinterpret_cast<unsigned long long*>(digits);
+    VP_HIP(ctx, hipMemsetAsync(digits, 0, (size_t)DIGIT_BINS * 8, st));
+    return launch<SELECT>(ctx, a, p, p.tile_lds + DIGIT_BINS * 4, st, "trial_pass_kernel<select>");
+}
 
 }  // namespace
 
@@ -225,63 +310,49 @@ size_t vp_trial_ranks_workspace_bytes(int Nt, int Ne, int D, long long NT) {
 int vp_trial_ranks_targets_f32(vp_ctx* ctx, const float* trials, const int* trial_labels, const long long* trial_offsets, int Nt,
                                const float* enroll, const int* enroll_labels, const int* enroll_ranks, int Ne, int D, long long NT,
                                float* targets, void* ws, size_t ws_bytes, vp_stream stream) {
-    if (!supported(Nt, Ne, D, NT)) TRIAL_UNSUP(ctx, "trial_ranks_targets");       // first, and without a context: needs no device
-    if (!ctx || !trials || !trial_labels || !trial_offsets || !enroll || !enroll_labels || !enroll_ranks || !targets || !ws)
-        VP_FAIL(ctx, VP_EINVAL, "trial_ranks_targets: null pointer");
-    const Plan p = plan(Nt, Ne, D, NT);
-    if (ws_bytes < p.bytes) VP_FAIL(ctx, VP_EWORKSPACE, "trial_ranks_targets: workspace %zu < %zu bytes", ws_bytes, p.bytes);
-    hipStream_t st = (hipStream_t)stream;
-    PassArgs a = common_args(p, ws, trial_labels, Nt, enroll_labels, Ne, D, NT);
-    hipLaunchKernelGGL(unit_rows_kernel, dim3((Nt + 3) / 4), dim3(256), 0, st, trials, (long long)Nt, D, (float*)ws);
-    VP_LAUNCH_CHECK(ctx, "unit_rows_kernel");
-    hipLaunchKernelGGL(unit_rows_kernel, dim3((Ne + 3) / 4), dim3(256), 0, st, enroll, (long long)Ne, D, (float*)((char*)ws + p.unit_t));
-    VP_LAUNCH_CHECK(ctx, "unit_rows_kernel");
-    a.toff = trial_offsets;
-    a.erank = enroll_ranks;
-    a.targets = targets;
-    return launch<TARGETS>(ctx, a, p, p.tile_lds, st, "trial_pass_kernel<targets>");
+    return targets_pass(ctx, "trial_ranks_targets", trials, trial_labels, trial_offsets, Nt, enroll, enroll_labels, enroll_ranks, Ne, D,
+                        NT, targets, nullptr, ws, ws_bytes, stream);
 }
 
 int vp_trial_ranks_counts_f32(vp_ctx* ctx, const int* trial_labels, int Nt, const int* enroll_labels, int Ne, int D,
                               const float* sorted_targets, long long NT, long long* hist, const void* ws, size_t ws_bytes,
                               vp_stream stream) {
-    if (!supported(Nt, Ne, D, NT)) TRIAL_UNSUP(ctx, "trial_ranks_counts");
-    if (!ctx || !trial_labels || !enroll_labels || !sorted_targets || !hist || !ws)
-        VP_FAIL(ctx, VP_EINVAL, "trial_ranks_counts: null pointer");
-    const Plan p = plan(Nt, Ne, D, NT);
-    if (ws_bytes < p.bytes) VP_FAIL(ctx, VP_EWORKSPACE, "trial_ranks_counts: workspace %zu < %zu bytes", ws_bytes, p.bytes);
-    hipStream_t st = (hipStream_t)stream;
-    PassArgs a = common_args(p, ws, trial_labels, Nt, enroll_labels, Ne, D, NT);
-    a.st = sorted_targets;
-    a.P = p.P;
-    a.stride = p.stride;
-    a.H = p.H;
-    a.hist = reinterpret_cast<unsigned long long*>(hist);
-    VP_HIP(ctx, hipMemsetAsync(hist, 0, (size_t)(NT + 1) * 8, st));
-    return launch<COUNTS>(ctx, a, p, p.count_lds, st, "trial_pass_kernel<counts>");
+    return counts_pass(ctx, "trial_ranks_counts", trial_labels, Nt, enroll_labels, Ne, D, sorted_targets, NT, hist, nullptr, ws,
+                       ws_bytes, stream);
 }
 
 int vp_trial_ranks_select_f32(vp_ctx* ctx, const int* trial_labels, int Nt, const int* enroll_labels, int Ne, int D, long long NT,
                               float lo, float hi, int level, long long prefix, long long* digits, const void* ws, size_t ws_bytes,
                               vp_stream stream) {
-    if (!supported(Nt, Ne, D, NT)) TRIAL_UNSUP(ctx, "trial_ranks_select");
-    if (!ctx || !trial_labels || !enroll_labels || !digits || !ws) VP_FAIL(ctx, VP_EINVAL, "trial_ranks_select: null pointer");
-    if (level < 0 || level > 2 || prefix < 0 || prefix > 0xffffffffLL) VP_FAIL(ctx, VP_EINVAL, "trial_ranks_select: level, prefix");
-    const Plan p = plan(Nt, Ne, D, NT);
-    if (ws_bytes < p.bytes) VP_FAIL(ctx, VP_EWORKSPACE, "trial_ranks_select: workspace %zu < %zu bytes", ws_bytes, p.bytes);
-    hipStream_t st = (hipStream_t)stream;
-    PassArgs a = common_args(p, ws, trial_labels, Nt, enroll_labels, Ne, D, NT);
-    static const int shifts[3] = {21, 10, 0};
-    static const unsigned masks[3] = {0u, 0xffe00000u, 0xfffffc00u}, digit_masks[3] = {2047u, 2047u, 1023u};
-    a.lo = lo;
-    a.hi = hi;
-    a.shift = shifts[level];
-    a.prefix_mask = masks[level];
-    a.prefix = (unsigned)prefix & masks[level];
-    a.digit_mask = digit_masks[level];
-    a.hist = reinterpret_cast<unsigned long long*>(digits);
-    VP_HIP(ctx, hipMemsetAsync(digits, 0, (size_t)DIGIT_BINS * 8, st));
-    return launch<SELECT>(ctx, a, p, p.tile_lds + DIGIT_BINS * 4, st, "trial_pass_kernel<select>");
+    return select_pass(ctx, "trial_ranks_select", trial_labels, Nt, enroll_labels, Ne, D, NT, lo, hi, level, prefix, digits, nullptr,
+                       ws, ws_bytes, stream);
+}
+
+int vp_trial_ranks_targets_norm_f32(vp_ctx* ctx, const float* trials, const int* trial_labels, const long long* trial_offsets, int Nt,
+                                    const float* enroll, const int* enroll_labels, const int* enroll_ranks, int Ne, int D,
+                                    long long NT, float* targets, const float* trial_mean, const float* trial_r,
+                                    const float* enroll_mean, const float* enroll_r, void* ws, size_t ws_bytes, vp_stream stream) {
+    const Norm nz{trial_mean, trial_r, enroll_mean, enroll_r};
+    return targets_pass(ctx, "trial_ranks_targets_norm", trials, trial_labels, trial_offsets, Nt, enroll, enroll_labels, enroll_ranks,
+                        Ne, D, NT, targets, &nz, ws, ws_bytes, stream);
+}
+
+int vp_trial_ranks_counts_norm_f32(vp_ctx* ctx, const int* trial_labels, int Nt, const int* enroll_labels, int Ne, int D,
+                                   const float* sorted_targets, long long NT, long long* hist, const float* trial_mean,
+                                   const float* trial_r, const float* enroll_mean, const float* enroll_r, const void* ws,
+                                   size_t ws_bytes, vp_stream stream) {
+    const Norm nz{trial_mean, trial_r, enroll_mean, enroll_r};
+    return counts_pass(ctx, "trial_ranks_counts_norm", trial_labels, Nt, enroll_labels, Ne, D, sorted_targets, NT, hist, &nz, ws,
+                       ws_bytes, stream);
+}
+
+int vp_trial_ranks_select_norm_f32(vp_ctx* ctx, const int* trial_labels, int Nt, const int* enroll_labels, int Ne, int D,
+                                   long long NT, float lo, float hi, int level, long long prefix, long long* digits,
+                                   const float* trial_mean, const float* trial_r, const float* enroll_mean, const float* enroll_r,
+                                   const void* ws, size_t ws_bytes, vp_stream stream) {
+    const Norm nz{trial_mean, trial_r, enroll_mean, enroll_r};
+    return select_pass(ctx, "trial_ranks_select_norm", trial_labels, Nt, enroll_labels, Ne, D, NT, lo, hi, level, prefix, digits, &nz,
+                       ws, ws_bytes, stream);
 }
 
 }  // extern "C"

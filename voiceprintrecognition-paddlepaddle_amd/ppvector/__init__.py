@@ -126,6 +126,23 @@ def get_trial_scorer():
     return _TRIAL_SCORER
 
 
+_SCORE_NORM = None
+
+
+def set_score_norm(score_norm):
+    """The adaptive score normalisation (AS-norm) that ``ppvector.metric.metrics.evaluate_trials`` applies when it is not handed one:
+    a ``ppvector.metric.score_norm.ScoreNorm`` (a cohort on the device and its top_n; csrc/cohort_stats.hip, docs/score_norm.md), or
+    None -- raw cosines, as the reference scores; the default."""
+    global _SCORE_NORM
+    if score_norm is not None and not (hasattr(score_norm, 'mean_r') and hasattr(score_norm, 'normalise')):
+        raise ValueError(f'unsupported score normalisation {score_norm!r}')
+    _SCORE_NORM = score_norm
+
+
+def get_score_norm():
+    return _SCORE_NORM
+
+
 _FUSED_GRID_KERNELS = True
 
 

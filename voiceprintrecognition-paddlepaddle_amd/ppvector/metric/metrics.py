@@ -1,7 +1,9 @@
 """EER / minDCF on the host (NumPy), semantics of ppvector/metric/metrics.py:4-37, plus the GPU
 trial scorer that replaces the per-trial sklearn loop of trainer.py:416-423: by default one cosine GEMM and the reference's
 arithmetic over all pairs; with ppvector.set_trial_scorer('fused') the same numbers from the sorted target scores and the counts of
-non-target scores between them, without the (Nt, Ne) matrix (csrc/trial_ranks.hip, docs/trial_ranks.md).
+non-target scores between them, without the (Nt, Ne) matrix (csrc/trial_ranks.hip, docs/trial_ranks.md).  Both scorers take an
+optional ``score_norm`` (ppvector.metric.score_norm.ScoreNorm, docs/score_norm.md; the reference has none): every cosine is then
+replaced by its adaptively normalised score z before anything is ranked.
 """
 import numpy as np
 
@@ -55,16 +57,22 @@ def cosine_score_matrix(trials, enroll):
     return out
 
 
-def evaluate_trials(enroll_features, enroll_labels, trials_features, trials_labels):
+def evaluate_trials(enroll_features, enroll_labels, trials_features, trials_labels, score_norm=None):
     """The scoring half of PPVectorTrainer.evaluate (ppvector/trainer.py:412-431): every trial embedding against every enrolled
     one (one cosine GEMM on the GPU instead of a Python loop of sklearn calls), target / non-target labels in the same
-    trial-major order, then the reference's fnr/fpr -> EER / minDCF arithmetic on the host.  Returns (eer, min_dcf, threshold)."""
+    trial-major order, then the reference's fnr/fpr -> EER / minDCF arithmetic on the host.  Returns (eer, min_dcf, threshold).
+    ``score_norm``: a ScoreNorm, or None for ppvector.get_score_norm() (None by default: raw cosines, as the reference)."""
     import numpy as np
     import torch
     import ppvector
+    if score_norm is None:
+        score_norm = ppvector.get_score_norm()
     if ppvector.get_trial_scorer() == 'fused':
-        return evaluate_trials_fused(enroll_features, enroll_labels, trials_features, trials_labels)
-    scores = cosine_score_matrix(torch.as_tensor(trials_features), torch.as_tensor(enroll_features)).cpu().numpy()
+        return evaluate_trials_fused(enroll_features, enroll_labels, trials_features, trials_labels, score_norm=score_norm)
+    scores = cosine_score_matrix(torch.as_tensor(trials_features), torch.as_tensor(enroll_features))
+    if score_norm is not None:
+        scores = score_norm.normalise(scores, torch.as_tensor(trials_features), torch.as_tensor(enroll_features))
+    scores = scores.cpu().numpy()
     el = np.asarray(enroll_labels).astype(np.int32)
     tl = np.asarray(trials_labels).astype(np.int32)
     all_score = scores.astype(np.float32).reshape(-1)
@@ -106,10 +114,11 @@ def _host_labels(labels):
 class TrialRanks:
     """The device side of the fused scorer (csrc/trial_ranks.hip): ``targets`` (NT,) float32 ascending and ``hist`` (NT + 1,) int64
     as device tensors, and the k-th smallest non-target of a bin on request.  ``Nt`` / ``Ne`` may be smaller than the buffers; ``ws``
-    is a caller's workspace (uint8, device)."""
+    is a caller's workspace (uint8, device).  ``score_norm`` (a ScoreNorm): every score, in all three passes, is z instead of the
+    cosine; the statistics are kept as ``stats`` = (trial mean, trial r, enrol mean, enrol r), device tensors."""
     DIGITS = ((21, 2048), (10, 2048), (0, 1024))         # shift and size of the three digits of vp_trial_ranks_select_f32
 
-    def __init__(self, trials, trial_labels, enroll, enroll_labels, Nt=None, Ne=None, ws=None):
+    def __init__(self, trials, trial_labels, enroll, enroll_labels, Nt=None, Ne=None, ws=None, score_norm=None):
         import torch
         from ppvector import _native as N
         trials, enroll = torch.as_tensor(trials), torch.as_tensor(enroll)
@@ -132,15 +141,19 @@ class TrialRanks:
         off, rank = torch.from_numpy(off).to(dev), torch.from_numpy(rank).to(dev)
         raw = torch.empty(self.NT, dtype=torch.float32, device=dev)
         lib, ctx = self._lib, self._ctx
+        self.stats = None if score_norm is None else score_norm.mean_r(self._t, self.Nt) + score_norm.mean_r(self._e, self.Ne)
+        stats = () if self.stats is None else tuple(t.data_ptr() for t in self.stats)
+        targets_pass = lib.vp_trial_ranks_targets_f32 if self.stats is None else lib.vp_trial_ranks_targets_norm_f32
+        counts_pass = lib.vp_trial_ranks_counts_f32 if self.stats is None else lib.vp_trial_ranks_counts_norm_f32
         with torch.cuda.device(dev):
-            N.check(lib.vp_trial_ranks_targets_f32(ctx, self._t.data_ptr(), self._tl.data_ptr(), off.data_ptr(), self.Nt,
-                                                   self._e.data_ptr(), self._el.data_ptr(), rank.data_ptr(), self.Ne, self.D, self.NT,
-                                                   raw.data_ptr(), self._ws.data_ptr(), self._ws.numel(), N.stream_ptr()), ctx)
+            N.check(targets_pass(ctx, self._t.data_ptr(), self._tl.data_ptr(), off.data_ptr(), self.Nt,
+                                 self._e.data_ptr(), self._el.data_ptr(), rank.data_ptr(), self.Ne, self.D, self.NT,
+                                 raw.data_ptr(), *stats, self._ws.data_ptr(), self._ws.numel(), N.stream_ptr()), ctx)
             self.targets = torch.sort(raw).values
             self.hist = torch.empty(self.NT + 1, dtype=torch.int64, device=dev)
-            N.check(lib.vp_trial_ranks_counts_f32(ctx, self._tl.data_ptr(), self.Nt, self._el.data_ptr(), self.Ne, self.D,
-                                                  self.targets.data_ptr(), self.NT, self.hist.data_ptr(), self._ws.data_ptr(),
-                                                  self._ws.numel(), N.stream_ptr()), ctx)
+            N.check(counts_pass(ctx, self._tl.data_ptr(), self.Nt, self._el.data_ptr(), self.Ne, self.D,
+                                self.targets.data_ptr(), self.NT, self.hist.data_ptr(), *stats, self._ws.data_ptr(),
+                                self._ws.numel(), N.stream_ptr()), ctx)
 
     def kth_nontarget(self, b, k):
         """The k-th smallest (k = 1 .. hist[b]) of the non-target scores of bin b, by three digit-counting passes."""
@@ -153,11 +166,13 @@ class TrialRanks:
         hi = float(self.targets[b]) if b < self.NT else float('inf')
         digits = torch.empty(2048, dtype=torch.int64, device=self._dev)
         key = 0
+        stats = () if self.stats is None else tuple(t.data_ptr() for t in self.stats)
+        select_pass = self._lib.vp_trial_ranks_select_f32 if self.stats is None else self._lib.vp_trial_ranks_select_norm_f32
         for level, (shift, size) in enumerate(self.DIGITS):
             with torch.cuda.device(self._dev):
-                N.check(self._lib.vp_trial_ranks_select_f32(self._ctx, self._tl.data_ptr(), self.Nt, self._el.data_ptr(), self.Ne,
-                                                            self.D, self.NT, lo, hi, level, key, digits.data_ptr(),
-                                                            self._ws.data_ptr(), self._ws.numel(), N.stream_ptr()), self._ctx)
+                N.check(select_pass(self._ctx, self._tl.data_ptr(), self.Nt, self._el.data_ptr(), self.Ne,
+                                    self.D, self.NT, lo, hi, level, key, digits.data_ptr(), *stats,
+                                    self._ws.data_ptr(), self._ws.numel(), N.stream_ptr()), self._ctx)
             upto = np.cumsum(digits[:size].cpu().numpy())
             d = int(np.searchsorted(upto, k, side='left'))
             if d >= size:
@@ -235,10 +250,10 @@ def eer_dcf_from_ranks(targets, hist, p_target=0.01, c_miss=1, c_fa=1):
     return float(eer), c_det / c_def, hi
 
 
-def evaluate_trials_fused(enroll_features, enroll_labels, trials_features, trials_labels):
+def evaluate_trials_fused(enroll_features, enroll_labels, trials_features, trials_labels, score_norm=None):
     """evaluate_trials without the (Nt, Ne) matrix: nothing on the device or the host grows with Nt * Ne.  Returns
-    (eer, min_dcf, threshold)."""
-    r = TrialRanks(trials_features, trials_labels, enroll_features, enroll_labels)
+    (eer, min_dcf, threshold).  ``score_norm``: a ScoreNorm, or None for raw cosines."""
+    r = TrialRanks(trials_features, trials_labels, enroll_features, enroll_labels, score_norm=score_norm)
     targets = r.targets.cpu().numpy()
     eer, min_dcf, where = eer_dcf_from_ranks(targets, r.hist.cpu().numpy())
     threshold = float(targets[where[1]]) if where[0] == 't' else r.kth_nontarget(where[1], where[2])

@@ -391,10 +391,59 @@ class PPVectorTrainer(object):
         if self.stop_eval:
             return -1, -1, -1
         eer, min_dcf, threshold = evaluate_trials(enroll_features, enroll_labels.cpu().numpy(), trials_features,
-                                                  trials_labels.cpu().numpy())
+                                                  trials_labels.cpu().numpy(), score_norm=self._score_norm())
         if save_image_path:
             _LOG.warning('save_image_path: the fnr/fpr plot (matplotlib) is not produced by this build')
         return float(eer), float(min_dcf), float(threshold)
+
+    # ------------------------------------------------------------------------------------------------ score normalisation
+    # An extension (docs/score_norm.md; the reference evaluates raw cosines only): dataset_conf.eval_conf.score_norm =
+    # {cohort: <.npy path, (C, D) float32>, top_n: 300}.  Absent or None: evaluate() scores exactly as without it.
+    def _score_norm(self):
+        conf = self.configs.dataset_conf.eval_conf.get('score_norm', None)
+        if conf is None:
+            return None
+        key = (str(conf.cohort), int(conf.get('top_n', 300)))
+        if getattr(self, '_score_norm_key', None) != key:       # the cohort is loaded and uploaded once
+            from ppvector.metric.score_norm import ScoreNorm
+            cohort = np.load(key[0])
+            if cohort.ndim != 2 or cohort.dtype != np.float32:
+                raise ValueError(f'eval_conf.score_norm.cohort {key[0]}: expected (C, D) float32, got {cohort.shape} {cohort.dtype}')
+            self._score_norm_obj, self._score_norm_key = ScoreNorm(torch.from_numpy(cohort).to(self.device), key[1]), key
+        return self._score_norm_obj
+
+    def extract_cohort(self, data_list_path, save_path=None, resume_model=None):
+        """The cohort of a score normalisation: embeds the utterances of a list (`path\\tlabel` lines, typically the training list) in
+        eval mode and returns the per-speaker means of the raw embeddings, (speakers, D) float32, speakers in ascending label order;
+        saved as .npy when save_path is given."""
+        if self.audio_featurizer is None:
+            self.audio_featurizer = AudioFeaturizer(feature_method=self.configs.preprocess_conf.feature_method,
+                                                    method_args=self.configs.preprocess_conf.get('method_args', {}))
+        conf = self.configs.dataset_conf
+        dataset_args = dict(conf.get('dataset', {}))
+        dataset_args['max_duration'] = conf.eval_conf.max_duration
+        dataset = PPVectorDataset(data_list_path=data_list_path, audio_featurizer=self.audio_featurizer, mode='eval', **dataset_args)
+        loader = _BatchLoader(dataset, batch_size=conf.eval_conf.batch_size,
+                              num_workers=int(dict(conf.get('dataLoader', {})).get('num_workers', 0)))
+        if self.model is None:
+            self.__setup_model(input_size=self.audio_featurizer.feature_dim)
+        if resume_model is not None:
+            if os.path.isdir(resume_model):
+                resume_model = os.path.join(resume_model, 'model.pdparams')
+            assert os.path.exists(resume_model), f"{resume_model} 模型不存在！"
+            self.model = load_pretrained(self.model, resume_model)
+        was_training = self.model.training
+        self.model.eval()
+        emb, labels = self._embed(loader, dataset, self.model if len(self.model) == 1 else self.model[0])
+        self.model.train(was_training)
+        if emb is None:
+            raise ValueError(f'extract_cohort: no utterance in {data_list_path}')
+        # a mean per speaker, ascending labels, each one reduction over that speaker's rows: no atomics, the same bits every run
+        cohort = torch.stack([emb[labels == s].mean(dim=0) for s in torch.unique(labels)]).cpu().numpy()
+        if save_path:
+            os.makedirs(os.path.dirname(os.path.abspath(save_path)), exist_ok=True)
+            np.save(save_path, cohort)
+        return cohort
 
     def export(self, save_model_path='models/', resume_model='models/CAMPPlus_Fbank/best_model/'):
         raise NotImplementedError('export writes a paddle.jit static graph (trainer.py:449-480); the MI355X engine loads '
