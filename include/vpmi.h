@@ -1153,8 +1153,39 @@ int vp_trial_ranks_select_f32(vp_ctx* ctx, const int* trial_labels, int Nt, cons
  * vp_trial_ranks_targets_norm_f32 / _counts_norm_f32 / _select_norm_f32 -- no reference call site: an extension.  The three passes
  *   of the trial scorer above with z in the place of the cosine: the same arguments, shapes, workspace and errors, and four more
  *   arrays, the trials' mean and r (Nt) and the enrolments' mean and r (Ne).  targets, sorted_targets, lo and hi are z values.
+ * vp_unit_rows_f32 -- no reference call site: an extension.  y (rows, D) = the unit rows of x (length in float64, one rounding per
+ *   element, a zero row stays zero): what vp_cohort_stats_f32 writes into its workspace, for a caller that keeps it.  rows >= 1,
+ *   D % 4 == 0, D <= 1024, else VP_EUNSUP.
+ * vp_cohort_stats_split_f32 -- no reference call site: an extension.  The statistics of vp_cohort_stats_f32 for FEW rows (the queries
+ *   of a search), with the cohort split over workgroups.  cohort_unit (C, D) is the cohort ALREADY as unit rows (vp_unit_rows_f32,
+ *   once per cohort, not per call); x (Q, D) are raw rows.  Grid (tiles of 32 rows, ranges): with slabs = ceil(C / 128),
+ *       slabs_per_wg = max(VP_COHORT_SPLIT_SLABS, ceil(slabs / VP_COHORT_SPLIT_MAX_RANGES)),  ranges = ceil(slabs / slabs_per_wg)
+ *   -- a function of C alone, not of Q, D, the device or its CU count, so a row's statistics do not depend on the batch it came in.
+ *   One launch per digit (W = 8, P = 4 passes; D >= 1020: W = 7, P = 5): a workgroup adds its LDS histogram to the tile's global
+ *   histogram of that pass with integer atomics (all histograms cleared by one memset on the stream), and the next launch's prologue
+ *   finds the digit; a sum launch leaves (#above, sum, sum of squares) per (tile, range, column) and a last kernel adds the ranges in
+ *   ascending order.  No float atomics, no grid barrier, no spinning, nothing depends on arrival order: two runs give the same bits,
+ *   and everything is stream work (capturable).  The float64 sums are added in another order than vp_cohort_stats_f32's: where they
+ *   are exact both return the same bits, elsewhere each is within 2e-6 of float64.
+ *   Workspace: ceil(Q / 32) (P (2^W + 2) 128 + 640 ranges) bytes.  1 <= Q <= VP_COHORT_SPLIT_MAX_Q (the caller chunks), C, top_n >= 1,
+ *   D % 4 == 0, D <= 1024, 16-byte aligned rows; anything else: the workspace query returns 0 and the entry point VP_EUNSUP (checked
+ *   before anything touches a device).  Null pointer: VP_EINVAL.  Workspace too small: VP_EWORKSPACE.
+ * vp_gallery_topk_norm_f32 -- no reference call site: an extension.  vp_gallery_topk_f32 with the SELECTION on z: the gallery row is
+ *   the enrolment, the query the trial; query_mean, query_r (Q) and user_mean, user_r (U) are their mean and r.  out_score holds z;
+ *   order: z descending, then row ascending.  Shapes, workspace (vp_gallery_topk_workspace_bytes), tail and errors are those of
+ *   vp_gallery_topk_f32; a null statistics pointer is VP_EINVAL.  The winners' raw cosines are not returned.
  * ---------------------------------------------------------------------------------------------- */
+#define VP_COHORT_SPLIT_SLABS 2
+#define VP_COHORT_SPLIT_MAX_RANGES 64
+#define VP_COHORT_SPLIT_MAX_Q 1024
 size_t vp_cohort_stats_workspace_bytes(int Q, int C, int D);
+int vp_unit_rows_f32(vp_ctx* ctx, const float* x, long long rows, int D, float* y, vp_stream stream);
+size_t vp_cohort_stats_split_workspace_bytes(int Q, int C, int D);
+int vp_cohort_stats_split_f32(vp_ctx* ctx, const float* x, int Q, const float* cohort_unit, int C, int D, int top_n, float* mean,
+                              float* std, void* ws, size_t ws_bytes, vp_stream stream);
+int vp_gallery_topk_norm_f32(vp_ctx* ctx, const float* queries, int Q, const float* centroids, int U, int D, int k,
+                             const float* query_mean, const float* query_r, const float* user_mean, const float* user_r, int* out_idx,
+                             float* out_score, void* ws, size_t ws_bytes, vp_stream stream);
 int vp_cohort_stats_f32(vp_ctx* ctx, const float* x, int Q, const float* cohort, int C, int D, int top_n, float* mean, float* std,
                         void* ws, size_t ws_bytes, vp_stream stream);
 int vp_score_norm_recip_f32(vp_ctx* ctx, const float* std, long long n, float* r, vp_stream stream);

@@ -14,6 +14,8 @@ of the f32 matrix-core peak (docs: MI355X 8 TB/s, 157.3 TFLOP/s), with the large
 Every number is a median with (min, max) of --iters calls.
 
 Usage: python tools/gallery_probe.py [--users 1000,100000,1000000] [--queries 1,32,256] [--k 1,10] [--iters 20] [--warmup 3]
+       python tools/gallery_probe.py --norm [--users 1000,100000] [--queries 1,32,256] [--k 1] [--cohort 6000] [--top-n 300]
+       (the search on normalised scores: norm_probe's docstring)
 """
 import argparse
 import os
@@ -41,8 +43,100 @@ def mmm(ts):
     return f'{statistics.median(ts):9.3f} ({min(ts):.3f}, {max(ts):.3f})'
 
 
+def norm_probe(a):
+    """--norm: the search on normalised scores (docs/gallery.md).  Per (U, Q), k = --k's first value, C = --cohort rows, top_n = --top-n,
+    five sides alternating call by call in one process, each timed by HIP events and by the host clock between two synchronisations:
+      split      SpeakerGallery.search with a score norm set: query statistics from vp_cohort_stats_split_f32 + r + the normalised search;
+      unsplit    (a) the same path with the query statistics from vp_cohort_stats_f32 (ScoreNorm.mean_r);
+      matrix     (b) what there was before: cosine_score_matrix (Q, U) + vp_score_norm_apply_f32 + torch.topk, with the query statistics
+                 from ScoreNorm.mean_r and the rows' statistics PREPARED (ScoreNorm.normalise itself recomputes them at every call);
+      z search   vp_gallery_topk_norm_f32 alone on prepared statistics;
+      cos search vp_gallery_topk_f32 alone (SpeakerGallery.search without a score norm): the z epilogue is the difference of the two."""
+    import torch
+    from ppvector import _native as N
+    from ppvector.infer_utils.gallery import SpeakerGallery
+    from ppvector.metric.metrics import cosine_score_matrix
+    from ppvector.metric.score_norm import ScoreNorm, recip_std
+    dev = torch.device('cuda', 0)
+    D, k = a.D, int(a.k.split(',')[0])
+    print(clocks(), flush=True)
+    print(f'D={D} C={a.cohort} top_n={a.top_n} k={k}; ms, median (min, max) of {a.iters} calls after {a.warmup} warm-up calls of every '
+          f'side; the sides alternate call by call; "ev" HIP events, "host" the host clock between two synchronisations')
+    gen = torch.Generator(device=dev).manual_seed(7)
+    spk = torch.randn(a.cohort // 3 + 1, D, generator=gen, device=dev)             # three cohort rows a speaker
+    cohort = spk.repeat_interleave(3, 0)[:a.cohort] * 1.8 * D ** -0.25 + torch.randn(a.cohort, D, generator=gen, device=dev)
+    sn = ScoreNorm(cohort, a.top_n)
+    lib, ctx = N.lib(), N.ctx(dev)
+    for U in [int(u) for u in a.users.split(',')]:
+        feats = spk[torch.randint(0, spk.shape[0], (U,), generator=gen, device=dev)] * 1.8 * D ** -0.25 + torch.randn(U, D, generator=gen, device=dev)
+        names = [f'u{i}' for i in range(U)]
+        gal, plain = SpeakerGallery(D, dev), SpeakerGallery(D, dev)
+        gal.rebuild(names, feats)
+        plain.rebuild(names, feats)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        gal.set_score_norm(sn)
+        torch.cuda.synchronize()
+        print(f'\nU={U}: set_score_norm (the rows\' statistics, vp_cohort_stats_f32 over {U} x {a.cohort}) {(time.perf_counter() - t0) * 1e3:.1f} ms', flush=True)
+        cen, um, ur = gal.centroids, gal._mean, gal._r
+        for Q in [int(q) for q in a.queries.split(',')]:
+            q = (feats[torch.randint(0, U, (Q,), generator=gen, device=dev)] + 0.3 * torch.randn(Q, D, generator=gen, device=dev)).contiguous()
+            ws = torch.empty(lib.vp_gallery_topk_workspace_bytes(Q, U, D, k), dtype=torch.uint8, device=dev)
+
+            def z_search(qm, qr):
+                idx = torch.empty((Q, k), dtype=torch.int32, device=dev)
+                z = torch.empty((Q, k), dtype=torch.float32, device=dev)
+                N.check(lib.vp_gallery_topk_norm_f32(ctx, q.data_ptr(), Q, cen.data_ptr(), U, D, k, qm.data_ptr(), qr.data_ptr(),
+                                                     um.data_ptr(), ur.data_ptr(), idx.data_ptr(), z.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                     N.stream_ptr()), ctx)
+                return idx, z
+
+            def matrix():
+                s = cosine_score_matrix(q, cen).contiguous()
+                qm, qr = sn.mean_r(q)
+                N.check(lib.vp_score_norm_apply_f32(ctx, s.data_ptr(), Q, U, qm.data_ptr(), qr.data_ptr(), um.data_ptr(), ur.data_ptr(),
+                                                    N.stream_ptr()), ctx)
+                z, idx = torch.topk(s, k, dim=1)
+                return idx, z
+
+            prepared = sn.mean_r_queries(q)
+            sides = {'split': lambda: gal.search(q, k), 'unsplit': lambda: z_search(*sn.mean_r(q)), 'matrix': matrix,
+                     'z search': lambda: z_search(*prepared), 'cos search': lambda: plain.search(q, k)}
+            for _ in range(a.warmup):
+                for fn in sides.values():
+                    fn()
+            ev, host, last = {n: [] for n in sides}, {n: [] for n in sides}, {}
+            iters = a.iters if Q * U <= 32 * 1000000 else max(5, a.iters // 2)
+            for _ in range(iters):
+                for name, fn in sides.items():
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    e0.record()
+                    last[name] = fn()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    host[name].append((time.perf_counter() - t0) * 1e3)
+                    ev[name].append(e0.elapsed_time(e1))
+            same = {n: int((last[n][0][:, 0].long() == last['split'][0][:, 0].long()).sum()) for n in ('unsplit', 'matrix', 'z search')}
+            dz = float((last['unsplit'][1] - last['split'][1]).abs().max())
+            for name in sides:
+                print(f'U={U:8d} Q={Q:4d} {name:10s} ev {mmm(ev[name])}   host {mmm(host[name])}', flush=True)
+            for clock, t in (('ev', ev), ('host', host)):
+                gain = statistics.median(t['unsplit']) - statistics.median(t['split'])
+                width = max(t['unsplit']) - min(t['unsplit'])
+                print(f'U={U:8d} Q={Q:4d} [{clock}] unsplit - split medians {gain:+.3f} ms against the unsplit side\'s own (min, max) width '
+                      f'{width:.3f} ms: split {"below by more than the width" if gain > width else "NOT below by more than the width"}')
+            print(f'U={U:8d} Q={Q:4d} same best row as split: {same} of {Q}; largest |z unsplit - z split| {dz:.3e}  ({iters} calls)', flush=True)
+        del gal, plain, feats
+    print(clocks(), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--norm', action='store_true', help='the search on normalised scores instead of the cosine search')
+    ap.add_argument('--cohort', type=int, default=6000)
+    ap.add_argument('--top-n', type=int, default=300)
     ap.add_argument('--users', default='1000,100000,1000000')
     ap.add_argument('--queries', default='1,32,256')
     ap.add_argument('--k', default='1,10')
@@ -55,6 +149,9 @@ def main():
     a = ap.parse_args()
     import numpy as np
     import torch
+    if a.norm:
+        assert torch.cuda.is_available(), 'needs an MI355X: the engine has no CPU fallback'
+        return norm_probe(a)
     from ppvector.infer_utils.gallery import SpeakerGallery
     from ppvector.metric.metrics import cosine_score_matrix
     assert torch.cuda.is_available(), 'needs an MI355X: the engine has no CPU fallback'

@@ -12,6 +12,8 @@
 //                          enters N - #above times, so ties at the N-th place need no rule.
 // Integer counts in LDS, float64 sums per lane in walk order, then lane halves, then the four waves in order: no float atomics, no
 // dependence on arrival order, no grid barrier, no spinning; two runs give the same bits.
+// vp_cohort_stats_split_f32  the same statistics for few rows, the cohort split over workgroups (below, in front of its kernels);
+// vp_unit_rows_f32         unit_rows_kernel on its own, for the caller that keeps the unit cohort.
 // vp_score_norm_recip_f32  r = 1 / max(std, floor);  vp_score_norm_apply_f32: z over an (Nt, Ne) cosine matrix in place -- the
 //                          arithmetic of score_norm.h, which the normalised passes of trial_ranks.hip share.
 #include "cos_tile.h"
@@ -154,6 +156,201 @@ __global__ __launch_bounds__(256) void cohort_stats_kernel(const StatsArgs a) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------ the cohort split over workgroups
+// vp_cohort_stats_split_f32: the same statistics for FEW rows (a search's queries), where one workgroup per tile leaves the chip idle.
+// Grid (tiles of 32 rows, ranges): a workgroup walks SPLIT_SLABS-or-more slabs of the unit cohort, one launch per digit and one for the
+// sums.  A digit's LDS histogram is added to the tile's global histogram of that pass (integer atomicAdd; one buffer per pass, all
+// cleared by one memset in front).  The NEXT launch's prologue scans the finished histogram -- every workgroup of a tile finds the same
+// (prefix, left) from the state the launch before it left in global memory, and the workgroup of range 0 leaves the new state for
+// the launch after it (a buffer per pass: nobody reads what is being written).  The sum pass leaves (#above, sum, sum of squares) per
+// (tile, range, column); the finalise kernel adds the ranges in ascending order.  No float atomics, no grid barrier, no spinning.
+constexpr int SPLIT_SLABS = VP_COHORT_SPLIT_SLABS;
+constexpr int SPLIT_MAX_RANGES = VP_COHORT_SPLIT_MAX_RANGES;
+constexpr int SPLIT_MAX_Q = VP_COHORT_SPLIT_MAX_Q;
+
+bool split_supported(int Q, int C, int D) { return supported(Q, C, D) && Q <= SPLIT_MAX_Q; }
+
+struct SplitPlan {
+    int qtiles, slabs_per_wg, ranges, digit_bits, passes;
+    size_t lds, hist_words, hist_bytes, state_bytes, sums_bytes, above_bytes, bytes;     // hist_words: one (pass, tile) histogram
+};
+
+// ranges depends on C alone (vpmi.h states it): a row's statistics do not depend on the batch it came in
+SplitPlan split_plan(int Q, int C, int D) {
+    SplitPlan p{};
+    const Plan u = plan(Q, C, D);
+    p.qtiles = u.qtiles;
+    p.digit_bits = u.digit_bits;
+    p.lds = u.lds;
+    p.passes = (32 + p.digit_bits - 1) / p.digit_bits;
+    const int by_cap = (u.slabs + SPLIT_MAX_RANGES - 1) / SPLIT_MAX_RANGES;
+    p.slabs_per_wg = by_cap > SPLIT_SLABS ? by_cap : SPLIT_SLABS;
+    p.ranges = (u.slabs + p.slabs_per_wg - 1) / p.slabs_per_wg;
+    p.hist_words = (size_t)QT << p.digit_bits;
+    p.hist_bytes = (size_t)p.qtiles * p.passes * p.hist_words * 4;
+    p.state_bytes = (size_t)p.qtiles * p.passes * 2 * QT * 4;
+    p.sums_bytes = (size_t)p.qtiles * p.ranges * QT * 16;
+    p.above_bytes = (size_t)p.qtiles * p.ranges * QT * 4;
+    p.bytes = p.hist_bytes + p.state_bytes + p.sums_bytes + p.above_bytes;     // every part a multiple of 128 bytes
+    return p;
+}
+
+struct SplitArgs {
+    const float* x;                     // (Q, D) raw rows
+    const float* cu;                    // (C, D) unit cohort rows
+    int Q, C, D, N;                     // N = min(top_n, C)
+    int slabs_per_wg, ranges, digit_bits, passes;
+    int pass;                           // 0 .. passes - 1: count that digit; passes: the sums
+    unsigned* hist;                     // [pass][tile][1 << digit_bits][32]
+    unsigned* state;                    // [pass][tile][2][32]: prefix and left AFTER that pass
+    double* sums;                       // [tile][range][32][2]
+    unsigned* above;                    // [tile][range][32]
+    float* mean;
+    float* std;
+};
+
+// (prefix, left) after pass `done` from the state after the pass before it and the finished histogram of `done`, by all 256 threads:
+// eight per column, each the total of an eighth of the digits; the one whose eighth holds the rank walks it from the largest digit down
+// (cohort_stats_kernel's scan, cut in eight).  Leaves them in LDS; the caller's barrier follows.
+__device__ __forceinline__ void split_pick(const SplitArgs& a, int done, int tile, unsigned* prefix, unsigned* left) {
+    const int W = a.digit_bits, top = 32 - done * W, bits = W < top ? W : top, sh = top - bits, nb = 1 << bits;
+    const int col = threadIdx.x >> 3, sub = threadIdx.x & 7, per = nb >> 3;        // nb is 256, 128 or 16
+    const unsigned* h = a.hist + ((size_t)done * gridDim.x + tile) * ((size_t)QT << W);
+    unsigned pre = 0u, k = (unsigned)a.N;
+    if (done) {
+        const unsigned* before = a.state + ((size_t)(done - 1) * gridDim.x + tile) * 2 * QT;
+        pre = before[col];
+        k = before[QT + col];
+    }
+    unsigned total = 0u;
+    for (int d = sub * per; d < (sub + 1) * per; ++d) total += h[d * QT + col];
+    unsigned higher = 0u;               // the counts of the eighths with larger digits
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const unsigned tj = __shfl(total, (threadIdx.x & 56) | j);
+        higher += j > sub ? tj : 0u;
+    }
+    if (higher < k && k <= higher + total) {    // exactly one of the eight: k <= the number of candidates, always
+        unsigned seen = higher;
+        int d = (sub + 1) * per - 1;
+        for (; d > sub * per; --d) {
+            const unsigned n = h[d * QT + col];
+            if (seen + n >= k) break;
+            seen += n;
+        }
+        prefix[col] = pre | (unsigned)d << sh;
+        left[col] = k - seen;
+    }
+}
+
+// grid (tiles of 32 embeddings, ranges), 256 threads, dynamic LDS as cohort_stats_kernel's
+__global__ __launch_bounds__(256) void cohort_split_pass_kernel(const SplitArgs a) {
+    extern __shared__ __align__(16) float smem[];
+    const int D = a.D, Dp = (D + 7) & ~7, W = a.digit_bits;
+    float* qs = smem;
+    unsigned* prefix = reinterpret_cast<unsigned*>(smem + (size_t)Dp * QT);
+    unsigned* left = prefix + QT;
+    unsigned* cnt = left + QT;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 31, half = lane >> 5;
+    const int tile = blockIdx.x, range = blockIdx.y;
+    const long long C = a.C;
+    const bool sum_pass = a.pass == a.passes;
+
+    cos_tile::load_tile<true>(qs, a.x, tile * QT, a.Q, D);
+    if (a.pass == 0) {
+        if (tid < QT) prefix[tid] = 0u;
+    } else {
+        split_pick(a, a.pass - 1, tile, prefix, left);
+        __syncthreads();
+        if (range == 0 && tid < 2 * QT) a.state[((size_t)(a.pass - 1) * gridDim.x + tile) * 2 * QT + tid] = prefix[tid];   // left follows
+    }
+    if (!sum_pass) {
+        const int top = 32 - a.pass * W, bits = W < top ? W : top, sh = top - bits, nb = 1 << bits;
+        const unsigned above_mask = top == 32 ? 0u : ~0u << top;
+        for (int i = tid; i < nb * QT; i += 256) cnt[i] = 0u;
+        __syncthreads();                // the tile, the prefix and the zeroed counts
+        const unsigned mine = prefix[c];
+        cos_tile::walk<long long>(qs, a.cu, C, D, range, a.slabs_per_wg, [&](long long r0, const cos_tile::f32x16& acc) {
+            const long long rb = r0 + 4 * half;
+#pragma unroll
+            for (int v = 0; v < 16; ++v) {
+                if (rb + 8 * (v >> 2) + (v & 3) >= C) continue;
+                const unsigned key = vp_order_key(acc[v]);
+                if ((key & above_mask) == mine) atomicAdd(&cnt[((key >> sh) & (nb - 1)) * QT + c], 1u);
+            }
+        });
+        __syncthreads();
+        unsigned* h = a.hist + ((size_t)a.pass * gridDim.x + tile) * ((size_t)QT << W);
+        for (int i = tid; i < nb * QT; i += 256) {
+            const unsigned n = cnt[i];
+            if (n) atomicAdd(&h[i], n);
+        }
+        return;
+    }
+    __syncthreads();                    // the tile and the threshold keys
+    const unsigned thr = prefix[c];
+    double s1 = 0.0, s2 = 0.0;
+    unsigned na = 0u;
+    cos_tile::walk<long long>(qs, a.cu, C, D, range, a.slabs_per_wg, [&](long long r0, const cos_tile::f32x16& acc) {
+        const long long rb = r0 + 4 * half;
+#pragma unroll
+        for (int v = 0; v < 16; ++v) {
+            if (rb + 8 * (v >> 2) + (v & 3) >= C || vp_order_key(acc[v]) <= thr) continue;
+            const double s = (double)acc[v];
+            s1 += s;
+            s2 += s * s;                // the square of an f32 is exact in float64
+            ++na;
+        }
+    });
+    s1 += __shfl_xor(s1, 32);
+    s2 += __shfl_xor(s2, 32);
+    na += __shfl_xor(na, 32);
+    double* part = reinterpret_cast<double*>(cnt);      // [wave][column][2], then the counts [wave][column]
+    unsigned* part_n = reinterpret_cast<unsigned*>(part + 4 * QT * 2);
+    if (half == 0) {
+        part[(w * QT + c) * 2 + 0] = s1;
+        part[(w * QT + c) * 2 + 1] = s2;
+        part_n[w * QT + c] = na;
+    }
+    __syncthreads();
+    if (tid < QT) {
+        double t1 = 0.0, t2 = 0.0;
+        unsigned n = 0u;
+        for (int i = 0; i < 4; ++i) {
+            t1 += part[(i * QT + tid) * 2 + 0];
+            t2 += part[(i * QT + tid) * 2 + 1];
+            n += part_n[i * QT + tid];
+        }
+        const size_t at = ((size_t)tile * a.ranges + range) * QT + tid;
+        a.sums[at * 2 + 0] = t1;
+        a.sums[at * 2 + 1] = t2;
+        a.above[at] = n;
+    }
+}
+
+// a thread per row: the ranges in ascending order, the threshold score N - #above times, the float64 tail
+__global__ __launch_bounds__(256) void cohort_split_finalise_kernel(const SplitArgs a) {
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= a.Q) return;
+    const int tile = q / QT, col = q % QT, tiles = (a.Q + QT - 1) / QT;
+    double t1 = 0.0, t2 = 0.0;
+    unsigned n = 0u;
+    for (int r = 0; r < a.ranges; ++r) {
+        const size_t at = ((size_t)tile * a.ranges + r) * QT + col;
+        t1 += a.sums[at * 2 + 0];
+        t2 += a.sums[at * 2 + 1];
+        n += a.above[at];
+    }
+    const unsigned thr = a.state[((size_t)(a.passes - 1) * tiles + tile) * 2 * QT + col];
+    const double t = (double)key_score(thr), k = (double)((unsigned)a.N - n);
+    t1 += k * t;
+    t2 += k * (t * t);
+    float m, sd;
+    score_norm::mean_std(t1, t2, a.N, m, sd);
+    a.mean[q] = m;
+    a.std[q] = sd;
+}
+
 __global__ __launch_bounds__(256) void recip_std_kernel(const float* __restrict__ std, long long n, float* __restrict__ r) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
         r[i] = score_norm::recip_std(std[i]);
@@ -206,6 +403,59 @@ int vp_cohort_stats_f32(vp_ctx* ctx, const float* x, int Q, const float* cohort,
     a.std = std;
     hipLaunchKernelGGL(cohort_stats_kernel, dim3(p.qtiles), dim3(256), p.lds, st, a);
     VP_LAUNCH_CHECK(ctx, "cohort_stats_kernel");
+    return VP_OK;
+}
+
+int vp_unit_rows_f32(vp_ctx* ctx, const float* x, long long rows, int D, float* y, vp_stream stream) {
+    if (rows < 1 || D < 4 || D % 4 != 0 || D > MAX_D || (rows + 3) / 4 > 0x7fffffffLL)
+        VP_FAIL(ctx, VP_EUNSUP, "unit_rows: rows >= 1, D %% 4 == 0, D <= %d", MAX_D);
+    if (!ctx || !x || !y) VP_FAIL(ctx, VP_EINVAL, "unit_rows: null pointer");
+    hipLaunchKernelGGL(unit_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, rows, D, y);
+    VP_LAUNCH_CHECK(ctx, "unit_rows_kernel");
+    return VP_OK;
+}
+
+size_t vp_cohort_stats_split_workspace_bytes(int Q, int C, int D) { return split_supported(Q, C, D) ? split_plan(Q, C, D).bytes : 0; }
+
+int vp_cohort_stats_split_f32(vp_ctx* ctx, const float* x, int Q, const float* cohort_unit, int C, int D, int top_n, float* mean,
+                              float* std, void* ws, size_t ws_bytes, vp_stream stream) {
+    if (!split_supported(Q, C, D) || top_n < 1)         // first, and without a context: needs no device
+        VP_FAIL(ctx, VP_EUNSUP, "cohort_stats_split: 1 <= Q <= %d, C, top_n >= 1, D %% 4 == 0, D <= %d", SPLIT_MAX_Q, MAX_D);
+    if (!ctx || !x || !cohort_unit || !mean || !std || !ws) VP_FAIL(ctx, VP_EINVAL, "cohort_stats_split: null pointer");
+    const SplitPlan p = split_plan(Q, C, D);
+    if (ws_bytes < p.bytes) VP_FAIL(ctx, VP_EWORKSPACE, "cohort_stats_split: workspace %zu < %zu bytes", ws_bytes, p.bytes);
+    hipStream_t st = (hipStream_t)stream;
+    static bool attr_dev[64] = {};              // the attribute is per device
+    bool& attr_set = attr_dev[ctx->device & 63];
+    if (!attr_set) {
+        VP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(cohort_split_pass_kernel),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS));
+        attr_set = true;
+    }
+    SplitArgs a{};
+    a.x = x;
+    a.cu = cohort_unit;
+    a.Q = Q;
+    a.C = C;
+    a.D = D;
+    a.N = top_n < C ? top_n : C;
+    a.slabs_per_wg = p.slabs_per_wg;
+    a.ranges = p.ranges;
+    a.digit_bits = p.digit_bits;
+    a.passes = p.passes;
+    a.hist = (unsigned*)ws;
+    a.state = (unsigned*)((char*)ws + p.hist_bytes);
+    a.sums = (double*)((char*)ws + p.hist_bytes + p.state_bytes);
+    a.above = (unsigned*)((char*)ws + p.hist_bytes + p.state_bytes + p.sums_bytes);
+    a.mean = mean;
+    a.std = std;
+    VP_HIP(ctx, hipMemsetAsync(a.hist, 0, p.hist_bytes, st));          // every pass's histograms, once
+    for (a.pass = 0; a.pass <= p.passes; ++a.pass) {                    // the digits, then the sums
+        hipLaunchKernelGGL(cohort_split_pass_kernel, dim3(p.qtiles, p.ranges), dim3(256), p.lds, st, a);
+        VP_LAUNCH_CHECK(ctx, "cohort_split_pass_kernel");
+    }
+    hipLaunchKernelGGL(cohort_split_finalise_kernel, dim3((Q + 255) / 256), dim3(256), 0, st, a);
+    VP_LAUNCH_CHECK(ctx, "cohort_split_finalise_kernel");
     return VP_OK;
 }
 

@@ -12,9 +12,13 @@
 //                            sorted partial list per (query, workgroup).
 //                            gallery_merge_kernel: a workgroup per query copies its partial lists to LDS and merges them (k rounds of a
 //                            block-wide best-head selection over sorted lists).
+// vp_gallery_topk_norm_f32   the same two kernels with gallery_score_kernel<true>: the value offered to the lists is score_norm.h's z of
+//                            the cosine (the gallery row is the enrolment, the query the trial; docs/gallery.md, "Search on normalised
+//                            scores"), so the selection itself is on z.  Nothing else differs: the lists, better(), the merge.
 // Order everywhere: score descending, then row ascending.  No atomics, no grid barrier, fixed order of every sum: two runs give the
 // same bits.  f32 throughout: a narrower gallery would change which rows win (the rule of diarize.hip's selection).
 #include "cos_tile.h"
+#include "score_norm.h"
 
 namespace {
 
@@ -81,9 +85,18 @@ __global__ __launch_bounds__(256) void gallery_centroid_kernel(const float* __re
 
 // ------------------------------------------------------------------------------------------------ scores and per-workgroup lists
 // grid (query tiles, row ranges), 256 threads, dynamic LDS: qs [Dp][32] | list scores [4][32][kp] | list rows [4][32][kp]
+// NORM: per query and per gallery row the mean of its top cohort scores and r = 1 / max(std, floor); the lists then hold z
+struct NormStats {
+    const float* qmean;
+    const float* qr;
+    const float* umean;
+    const float* ur;
+};
+
+template <bool NORM>
 __global__ __launch_bounds__(256) void gallery_score_kernel(const float* __restrict__ queries, int Q, const float* __restrict__ G, int U,
                                                             int D, int k, int slabs_per_wg, int ranges, float* __restrict__ part_s,
-                                                            int* __restrict__ part_i) {
+                                                            int* __restrict__ part_i, const NormStats nz) {
     extern __shared__ __align__(16) float smem[];
     const int Dp = (D + 7) & ~7;
     float* qs = smem;
@@ -100,7 +113,17 @@ __global__ __launch_bounds__(256) void gallery_score_kernel(const float* __restr
     float* my_s = ls + (w * QT + c) * kp;        // the list of (this wave, query c): shared by the lanes c and c + 32, which take turns
     const bool my_q = qt * QT + c < Q;           // the tile's columns past Q are zero queries: nothing is kept for them
     int* my_i = li + (w * QT + c) * kp;
-    cos_tile::walk<int>(qs, G, U, D, range, slabs_per_wg, [&](int r0, const cos_tile::f32x16& acc) {
+    float mq = 0.f, rq = 0.f;
+    if (NORM && my_q) { mq = nz.qmean[qt * QT + c]; rq = nz.qr[qt * QT + c]; }
+    cos_tile::walk<int>(qs, G, U, D, range, slabs_per_wg, [&](int r0, const cos_tile::f32x16& cosines) {
+        cos_tile::f32x16 acc = cosines;         // what is offered to the list: the cosine, or its z
+        if (NORM) {
+#pragma unroll
+            for (int v = 0; v < 16; ++v) {
+                const int r = r0 + 4 * half + 8 * (v >> 2) + (v & 3);
+                if (my_q && r < U) acc[v] = score_norm::z(cosines[v], nz.umean[r], nz.ur[r], mq, rq);
+            }
+        }
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             if (half == h) {
@@ -261,6 +284,32 @@ __global__ __launch_bounds__(256) void gallery_merge_kernel(const float* __restr
     }
 }
 
+// the two launches of a search; the callers have checked the shape and the pointers
+template <bool NORM>
+int topk(vp_ctx* ctx, const float* queries, int Q, const float* centroids, int U, int D, int k, const NormStats& nz, int* out_idx,
+         float* out_score, void* ws, size_t ws_bytes, vp_stream stream) {
+    const Plan p = plan(Q, U, D, k);
+    if (ws_bytes < p.bytes) VP_FAIL(ctx, VP_EWORKSPACE, "gallery_topk: workspace %zu < %zu bytes", ws_bytes, p.bytes);
+    hipStream_t st = (hipStream_t)stream;
+    static bool attr_dev[64] = {};              // the attribute is per device (and per instantiation: the static is the template's)
+    bool& attr_set = attr_dev[ctx->device & 63];
+    if (!attr_set) {
+        VP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(gallery_score_kernel<NORM>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, MAX_D * QT * 4 + 4 * QT * MAX_K * 8));
+        VP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(gallery_merge_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        MAX_RANGES * MAX_K * 8));
+        attr_set = true;
+    }
+    float* part_s = (float*)ws;
+    int* part_i = (int*)((char*)ws + p.part_bytes);
+    hipLaunchKernelGGL(gallery_score_kernel<NORM>, dim3(p.qtiles, p.ranges), dim3(256), p.lds, st, queries, Q, centroids, U, D, k,
+                       p.slabs_per_wg, p.ranges, part_s, part_i, nz);
+    VP_LAUNCH_CHECK(ctx, "gallery_score_kernel");
+    hipLaunchKernelGGL(gallery_merge_kernel, dim3(Q), dim3(256), p.merge_lds, st, part_s, part_i, p.ranges, k, out_idx, out_score);
+    VP_LAUNCH_CHECK(ctx, "gallery_merge_kernel");
+    return VP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -283,26 +332,18 @@ int vp_gallery_topk_f32(vp_ctx* ctx, const float* queries, int Q, const float* c
     if (!supported(Q, U, D, k))                 // first, and without a context: the refusal needs no device
         VP_FAIL(ctx, VP_EUNSUP, "gallery_topk: Q, U >= 1, D %% 4 == 0, D <= %d, 1 <= k <= %d, U D < 2^31", MAX_D, MAX_K);
     if (!ctx || !queries || !centroids || !out_idx || !out_score || !ws) VP_FAIL(ctx, VP_EINVAL, "gallery_topk: null pointer");
-    const Plan p = plan(Q, U, D, k);
-    if (ws_bytes < p.bytes) VP_FAIL(ctx, VP_EWORKSPACE, "gallery_topk: workspace %zu < %zu bytes", ws_bytes, p.bytes);
-    hipStream_t st = (hipStream_t)stream;
-    static bool attr_dev[64] = {};              // the attribute is per device
-    bool& attr_set = attr_dev[ctx->device & 63];
-    if (!attr_set) {
-        VP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(gallery_score_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        MAX_D * QT * 4 + 4 * QT * MAX_K * 8));
-        VP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(gallery_merge_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        MAX_RANGES * MAX_K * 8));
-        attr_set = true;
-    }
-    float* part_s = (float*)ws;
-    int* part_i = (int*)((char*)ws + p.part_bytes);
-    hipLaunchKernelGGL(gallery_score_kernel, dim3(p.qtiles, p.ranges), dim3(256), p.lds, st, queries, Q, centroids, U, D, k,
-                       p.slabs_per_wg, p.ranges, part_s, part_i);
-    VP_LAUNCH_CHECK(ctx, "gallery_score_kernel");
-    hipLaunchKernelGGL(gallery_merge_kernel, dim3(Q), dim3(256), p.merge_lds, st, part_s, part_i, p.ranges, k, out_idx, out_score);
-    VP_LAUNCH_CHECK(ctx, "gallery_merge_kernel");
-    return VP_OK;
+    return topk<false>(ctx, queries, Q, centroids, U, D, k, NormStats{}, out_idx, out_score, ws, ws_bytes, stream);
+}
+
+int vp_gallery_topk_norm_f32(vp_ctx* ctx, const float* queries, int Q, const float* centroids, int U, int D, int k,
+                             const float* query_mean, const float* query_r, const float* user_mean, const float* user_r, int* out_idx,
+                             float* out_score, void* ws, size_t ws_bytes, vp_stream stream) {
+    if (!supported(Q, U, D, k))
+        VP_FAIL(ctx, VP_EUNSUP, "gallery_topk_norm: Q, U >= 1, D %% 4 == 0, D <= %d, 1 <= k <= %d, U D < 2^31", MAX_D, MAX_K);
+    if (!ctx || !queries || !centroids || !out_idx || !out_score || !ws) VP_FAIL(ctx, VP_EINVAL, "gallery_topk_norm: null pointer");
+    if (!query_mean || !query_r || !user_mean || !user_r) VP_FAIL(ctx, VP_EINVAL, "gallery_topk_norm: null statistics pointer");
+    return topk<true>(ctx, queries, Q, centroids, U, D, k, NormStats{query_mean, query_r, user_mean, user_r}, out_idx, out_score, ws,
+                      ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -41,6 +41,50 @@ def cohort_stats(embeddings, cohort, top_n=300, Q=None, C=None, ws=None):
     return mean, std
 
 
+def unit_rows(x):
+    """(rows, D) raw rows, a GPU tensor -> their unit rows as the kernels form them (length in float64, one rounding per element)."""
+    import torch
+    from ppvector import _native as N
+    x = _device_rows(x, 'unit_rows')
+    y = torch.empty_like(x)
+    ctx = N.ctx(x.device)
+    with torch.cuda.device(x.device):
+        N.check(N.lib().vp_unit_rows_f32(ctx, x.data_ptr(), x.shape[0], x.shape[1], y.data_ptr(), N.stream_ptr()), ctx)
+    return y
+
+
+def cohort_stats_split(embeddings, cohort_unit, top_n=300, Q=None, C=None, ws=None):
+    """``cohort_stats`` for few rows (a search's queries), the cohort split over workgroups (vp_cohort_stats_split_f32).
+    ``cohort_unit`` is the cohort ALREADY as unit rows (``unit_rows``, ``ScoreNorm.unit_cohort``).  More rows than
+    VP_COHORT_SPLIT_MAX_Q go in chunks: a row's statistics do not depend on its chunk.  ``ws``: a caller's workspace (uint8, device)
+    for a call of one chunk."""
+    import torch
+    from ppvector import _native as N
+    x = _device_rows(embeddings, 'cohort_stats_split')
+    cu = _device_rows(cohort_unit, 'cohort_stats_split', x.device)
+    Q = x.shape[0] if Q is None else int(Q)
+    C = cu.shape[0] if C is None else int(C)
+    D, top_n = x.shape[1], int(top_n)
+    if cu.shape[1] != D:
+        raise ValueError(f'cohort_stats_split: embeddings have D = {D}, the cohort has D = {cu.shape[1]}')
+    lib, ctx = N.lib(), N.ctx(x.device)
+    cap = N.VP_COHORT_SPLIT_MAX_Q
+    if Q < 1 or top_n < 1 or lib.vp_cohort_stats_split_workspace_bytes(min(Q, cap), C, D) == 0:
+        raise N.VpmiError(f'cohort_stats_split: unsupported shape Q={Q} C={C} D={D} top_n={top_n} '
+                          f'(Q, C, top_n >= 1, D % 4 == 0, D <= 1024)')
+    mean = torch.empty(Q, dtype=torch.float32, device=x.device)
+    std = torch.empty(Q, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        for first in range(0, Q, cap):
+            n = min(cap, Q - first)
+            need = lib.vp_cohort_stats_split_workspace_bytes(n, C, D)
+            if ws is None or ws.numel() < need:
+                ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+            N.check(lib.vp_cohort_stats_split_f32(ctx, x[first:].data_ptr(), n, cu.data_ptr(), C, D, top_n, mean[first:].data_ptr(),
+                                                  std[first:].data_ptr(), ws.data_ptr(), ws.numel(), N.stream_ptr()), ctx)
+    return mean, std
+
+
 def recip_std(std):
     """r = 1 / max(std, 1e-6) in float32, on the device."""
     import torch
@@ -65,6 +109,27 @@ class ScoreNorm:
             cohort = cohort.to(N.default_device())
         self.cohort = _device_rows(cohort, 'ScoreNorm')
         self.top_n = int(top_n)
+        self._unit = None
+        self._query_ws = None
+
+    def unit_cohort(self):
+        """The cohort as unit rows, made once: what the split statistics of a search's queries read."""
+        if self._unit is None:
+            self._unit = unit_rows(self.cohort)
+        return self._unit
+
+    def mean_r_queries(self, emb, n=None):
+        """``mean_r`` for the queries of a search: the cohort split over workgroups (csrc/cohort_stats.hip), chunked past the entry
+        point's largest Q.  Where the float64 sums are exact these are ``mean_r``'s bits; elsewhere both are within 2e-6 of float64."""
+        import torch
+        from ppvector import _native as N
+        x = _device_rows(emb, 'ScoreNorm.mean_r_queries', self.cohort.device)
+        n = x.shape[0] if n is None else int(n)
+        need = N.lib().vp_cohort_stats_split_workspace_bytes(min(n, N.VP_COHORT_SPLIT_MAX_Q), self.cohort.shape[0], x.shape[1])
+        if self._query_ws is None or self._query_ws.numel() < need:
+            self._query_ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+        mean, std = cohort_stats_split(x, self.unit_cohort(), self.top_n, Q=n, ws=self._query_ws)
+        return mean, recip_std(std)
 
     def stats(self, emb, n=None):
         """(mean, std) of the first n (default: all) rows of emb."""

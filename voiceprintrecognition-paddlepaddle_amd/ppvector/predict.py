@@ -123,6 +123,8 @@ class PPVectorPredictor:
         self.audio_feature = None
         self.users_name, self.users_audio_path = [], []
         self.gallery = None                                    # SpeakerGallery, made with the first enrolled embedding's width
+        self.score_norm = None                                 # a ScoreNorm: set_score_norm (docs/gallery.md)
+        self._cosine_threshold = None                          # the threshold in force when the score norm was set
         self.audio_db_path = audio_db_path
         self.speaker_diarize = SpeakerDiarization()
         if self.audio_db_path is not None:
@@ -147,7 +149,30 @@ class PPVectorPredictor:
     def __gallery(self):
         if self.gallery is None:
             self.gallery = SpeakerGallery(self.audio_feature.shape[1], self.device)
+            self.gallery.set_score_norm(self.score_norm)
         return self.gallery
+
+    def set_score_norm(self, score_norm, threshold=None):
+        """Adaptive score normalisation for ``recognition``, ``recognition_batch``, ``contrast`` and the ``search_audio_db`` branch
+        (no counterpart in the reference; docs/gallery.md): with a ``ScoreNorm`` they return, and threshold on, z.  ``threshold``
+        is the operating point on z and has to be given: a z is not a cosine, the constructor's threshold does not carry over.
+        ``set_score_norm(None)`` restores the cosine search and the threshold that was in force before."""
+        from ppvector.metric.score_norm import ScoreNorm
+        if score_norm is None:
+            if self.score_norm is not None:
+                self.threshold = self._cosine_threshold
+            self.score_norm = self._cosine_threshold = None
+        else:
+            if not isinstance(score_norm, ScoreNorm):
+                raise ValueError(f'set_score_norm: a ScoreNorm or None, got {type(score_norm).__name__}')
+            if threshold is None:
+                raise TypeError('set_score_norm: a threshold on z has to be given with a ScoreNorm (a z is not a cosine)')
+            if self.score_norm is None:
+                self._cosine_threshold = self.threshold
+            self.score_norm = score_norm
+            self.threshold = threshold
+        if self.gallery is not None:
+            self.gallery.set_score_norm(self.score_norm)
 
     def __gallery_set(self, user_name):
         """One user's row of the gallery from that user's rows of ``audio_feature``."""
@@ -232,9 +257,12 @@ class PPVectorPredictor:
         return np.concatenate(outs, axis=0)
 
     def contrast(self, audio_data1, audio_data2):
-        """声纹对比 -> cosine similarity."""
+        """声纹对比 -> cosine similarity; with a score norm set, the z of the pair (the first as trial, the second as enrolment)."""
         f = np.stack([self.predict(audio_data1), self.predict(audio_data2)])
-        s = cosine_score_matrix(torch.from_numpy(f[:1]).to(self.device), torch.from_numpy(f[1:]).to(self.device))
+        a, b = torch.from_numpy(f[:1]).to(self.device), torch.from_numpy(f[1:]).to(self.device)
+        s = cosine_score_matrix(a, b)
+        if self.score_norm is not None:
+            s = self.score_norm.normalise(s.contiguous(), a, b)
         return float(s[0, 0])
 
     def _want_bf16(self):
