@@ -54,6 +54,9 @@ __device__ __forceinline__ float2 cmul(float2 a, float2 b) {
     return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
 }
 
+// max(e, floor) that keeps a NaN (fmaxf would return the floor): a NaN inside a frame's window poisons that frame, as in the reference
+__device__ __forceinline__ float floor_keep_nan(float e, float floor) { return e < floor ? floor : e; }
+
 __global__ __launch_bounds__(FB_WAVES * 64) void fbank_frames_kernel(FbankArgs a) {
     __shared__ float s_win[FB_MAX_WIN];
     __shared__ float s_melw[FB_MAX_NNZ];
@@ -205,7 +208,7 @@ __global__ __launch_bounds__(FB_WAVES * 64) void fbank_frames_kernel(FbankArgs a
             return e;
         };
         if (lane < a.n_mels) {
-            const float v = logf(fmaxf(mel_dot(lane, 0, 1), a.log_floor));
+            const float v = logf(floor_keep_nan(mel_dot(lane, 0, 1), a.log_floor));
             orow[lane] = v;
             acc0 += v;
         }
@@ -216,7 +219,7 @@ __global__ __launch_bounds__(FB_WAVES * 64) void fbank_frames_kernel(FbankArgs a
             float e = m < a.n_mels ? mel_dot(m, sub, lpb) : 0.f;
             if (lpb >= 2) e += __shfl_xor(e, 1);
             if (lpb >= 4) e += __shfl_xor(e, 2);
-            const float v = logf(fmaxf(e, a.log_floor));
+            const float v = logf(floor_keep_nan(e, a.log_floor));
             if (m < a.n_mels && sub == 0) orow[m] = v;
             // column sum slot lane + 64 belongs to bin 64 + lane: hand the value to that lane
             const float vv = __shfl(v, (lane * lpb) & 63);
@@ -363,8 +366,11 @@ __global__ __launch_bounds__(FB_WAVES * 64, 3) void fbank_frames16_kernel(Fbank1
             x[n1] = __builtin_bit_cast(v2f, raw[n1]);       // whole-vector cast (an element-wise bit_cast of an ext-vector lvalue reads element 0)
         }
         const int i0 = 32 * n1 + 2 * j;
-        if (n1 < NP1 - 1 && NP1 < 16) part += x[n1].x + x[n1].y;                 // NP1 = ceil(win / 32): only the last row can cross the window end
-        else part += (i0 < a.win ? x[n1].x : 0.f) + (i0 + 1 < a.win ? x[n1].y : 0.f);
+        // NP1 = ceil(win / 32): for NP1 < 16 only the last row can cross the window end.  A sample past it is not the frame's (it may
+        // lie past the utterance, in a staging buffer nobody wrote): it is dropped here by a select -- the zero window weight alone
+        // would turn a NaN or Inf there into NaN * 0 = NaN
+        if (!(n1 < NP1 - 1 && NP1 < 16)) x[n1] = v2f{i0 < a.win ? x[n1].x : 0.f, i0 + 1 < a.win ? x[n1].y : 0.f};
+        part += x[n1].x + x[n1].y;
     }
     if (id + (int)gridDim.x < total) fetch(id + gridDim.x);
     if (a.remove_dc) {
@@ -457,7 +463,7 @@ __global__ __launch_bounds__(FB_WAVES * 64, 3) void fbank_frames16_kernel(Fbank1
                 const float p2 = *reinterpret_cast<const float*>(pp + q * 4 + 8), p3 = *reinterpret_cast<const float*>(pp + q * 4 + 12);
                 e0 += w0 * p0; e1 += w1 * p1; e0 += w2 * p2; e1 += w3 * p3;
             }
-            const float val = __logf(fmaxf(e0 + e1, a.log_floor));
+            const float val = __logf(floor_keep_nan(e0 + e1, a.log_floor));
             if (m < a.n_mels && tvalid) { orow[m] = val; csum[r] = val; }
         }
     }

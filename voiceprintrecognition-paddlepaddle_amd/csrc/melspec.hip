@@ -175,7 +175,7 @@ __global__ __launch_bounds__(WAVES * 64) void melspec_frames_kernel(MelArgs a) {
                 }
                 e += wq[0] * pq[0]; e += wq[1] * pq[1]; e += wq[2] * pq[2]; e += wq[3] * pq[3];
             }
-            if (a.log_db) e = 10.f * log10f(fmaxf(e, a.amin)) - a.db_off;
+            if (a.log_db) e = 10.f * log10f(e < a.amin ? a.amin : e) - a.db_off;      // not fmaxf: a NaN (a NaN sample in the frame) stays NaN, as in the reference
             orow[m] = e;
             if (it == 0) acc0 += e; else acc1 += e;
         }

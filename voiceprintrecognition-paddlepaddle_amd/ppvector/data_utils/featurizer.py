@@ -23,6 +23,40 @@ _KALDI_FIXED = {'dither': 0.0, 'window_type': 'povey', 'snip_edges': True, 'use_
                 'vtln_high': -500.0}
 
 
+def _f32(x):
+    return C.c_float(x).value
+
+
+def _fbank_pcm16_covered(o):
+    """Whether vp_fbank_cmn_pcm16 takes these options: the 16-bit loads exist in the four-frames-per-wave kernel only, which wants
+    an even frame shift (4-byte aligned sample pairs) and a mel bank that fits its padded round layout -- csrc/fbank.hip,
+    build_tables: rounds of 16 filters, taps padded to the round's longest filter rounded up to 4, at most F16_MAX_TAPS = 32 per
+    round and F16_MAX_WPAD = 1536 floats in all.  Decided here, up front, so that int16 input of an option set the entry does not
+    cover is widened first instead of failing in the library (the paddleaudio default n_mels=23 at 16 kHz is such a bank).  Option
+    sets the library refuses altogether report False: the float entry then raises its own error."""
+    win = int(_f32(_f32(o.sample_rate * o.frame_length_ms) * _f32(0.001)))          # the library's float32 products, truncated
+    shift = int(_f32(_f32(o.sample_rate * o.frame_shift_ms) * _f32(0.001)))
+    nfft = 1
+    while nfft < win:
+        nfft <<= 1
+    if nfft != 512 or win < 2 or shift < 1 or shift & 1 or not 1 <= o.n_mels <= 128:
+        return False
+
+    def mel(f):
+        return 1127.0 * math.log(1.0 + f / 700.0)
+    hi = o.high_freq if o.high_freq > 0.0 else o.high_freq + 0.5 * o.sample_rate
+    mlo = mel(o.low_freq)
+    delta = (mel(hi) - mlo) / (o.n_mels + 1)
+    bins = [mel(o.sample_rate / nfft * k) for k in range(nfft // 2)]
+    taps = []
+    for m in range(o.n_mels):
+        l, c, r = mlo + m * delta, mlo + (m + 1) * delta, mlo + (m + 2) * delta
+        nz = [k for k, x in enumerate(bins) if min((x - l) / (c - l), (r - x) / (r - c)) > 0.0]
+        taps.append(nz[-1] - nz[0] + 1 if nz else 0)
+    padded = [max(4, (max(taps[i:i + 16]) + 3) // 4 * 4) for i in range(0, o.n_mels, 16)]
+    return max(padded) <= 32 and 16 * sum(padded) <= 1536
+
+
 class AudioFeaturizer(nn.Module):
     """音频特征器 (feature_method: 'Fbank' on the HIP engine).
 
@@ -36,6 +70,7 @@ class AudioFeaturizer(nn.Module):
         self._feature_method = feature_method
         if feature_method == 'Fbank':
             self._opts = self._fbank_opts(method_args)
+            self._pcm16_ok = _fbank_pcm16_covered(self._opts)
         elif feature_method == 'MelSpectrogram':
             self._opts = self._mel_opts(method_args)
         elif feature_method == 'LogMelSpectrogram':
@@ -119,8 +154,10 @@ class AudioFeaturizer(nn.Module):
         if not waveforms.is_cuda:
             raise N.VpmiError('AudioFeaturizer needs GPU tensors: the engine has no CPU fallback')
         # 16-bit PCM as decoded (torch.int16): widened inside the Fbank frame kernel (x 1 / 32768, what the reference's readers do on
-        # the host), so an upload in front of this call carries half the bytes; other methods widen first
-        pcm16 = waveforms.dtype == torch.int16 and self._feature_method == 'Fbank' and waveforms.shape[-1] % 2 == 0
+        # the host), so an upload in front of this call carries half the bytes; other methods, an odd row length and Fbank options
+        # the 16-bit entry does not cover (_fbank_pcm16_covered) widen first
+        pcm16 = (waveforms.dtype == torch.int16 and self._feature_method == 'Fbank' and waveforms.shape[-1] % 2 == 0
+                 and self._pcm16_ok)
         if waveforms.dtype == torch.int16 and not pcm16:
             waveforms = waveforms.float() * (1.0 / 32768.0)
         wav = waveforms.contiguous() if pcm16 else waveforms.contiguous().float()
