@@ -1204,6 +1204,50 @@ int vp_trial_ranks_select_norm_f32(vp_ctx* ctx, const int* trial_labels, int Nt,
                                    const float* trial_mean, const float* trial_r, const float* enroll_mean, const float* enroll_r,
                                    const void* ws, size_t ws_bytes, vp_stream stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Energy voice-activity detection (csrc/vad.hip, docs/vad.md).  No reference call site: an extension.  It stands in for the call at
+ * speaker_diarization.py:37, yeaudio's model-based AudioSegment.vad, whose model has no weights here; it is a detector of this
+ * project's own and does not reproduce that model's regions.  f32 throughout, a ragged batch of B >= 1 recordings (B <= 65535).
+ * Integer counts only: no float atomics, no spinning; two runs give the same bits.  Both launched entry points copy their B + 1
+ * offsets to the host once (one stream synchronisation, nothing of the size of the audio) to check them: not capturable.
+ * vp_vad_num_frames -- F = n < win ? 0 : 1 + (n - win) / hop, snip-edges as vp_fbank_num_frames; 0 for win, hop < 1 or n < 0.
+ * vp_vad_frame_db_f32 -- no reference call site: an extension.  wave holds the recordings back to back; offsets (B + 1, device):
+ *   recording b is samples offsets[b] .. offsets[b+1]-1, n_b of them, and has F_b = vp_vad_num_frames(n_b, win, hop) frames; frame t
+ *   covers samples [t hop, t hop + win) of its own recording.  Per frame f[0 .. win): m = mean f, y[i] = (f[i] - m) - preemph
+ *   (f[max(i-1, 0)] - m) (the front end of vp_fbank_f32 without a window function; preemph = 0 switches it off), p = mean y^2 (two
+ *   passes over the staged samples: a large DC offset under a quiet signal is harmless), e = 10 log10(max(p, 1e-10)): digital
+ *   silence is exactly -100.  e[frame_offsets[b] + t]; frame_offsets (B + 1, device) with frame_offsets[b+1] - frame_offsets[b] ==
+ *   F_b; nothing outside [frame_offsets[0], frame_offsets[B]) is written.  Every sample is read from global memory once.
+ *   1 <= hop <= win <= 4096, 0 <= preemph < 1, offsets and frame_offsets non-decreasing from a start >= 0 and consistent with each
+ *   other, else VP_EINVAL; nothing is launched then.
+ * vp_vad_regions_f32 -- no reference call site: an extension.  Per recording b with F = frame_offsets[b+1] - frame_offsets[b]
+ *   frames of e, in this order:
+ *   1. F == 0: counts[b] = 0, thr[b] = (0, 0, 0, 0), nothing else.
+ *   2. fl = the ascending order statistic of e at rank floor((double)floor_pct (F - 1)), pk = the one at rank floor((double)peak_pct
+ *      (F - 1)): exact, by a radix selection on the order-preserving key of the trial scorer above; no interpolation.
+ *   3. r = pk - fl, on = fl + fmaxf(margin_db, onset r), off = fl + fmaxf(margin_db, offset r), f32, every operation rounded on its
+ *      own.  thr[b] = (fl, pk, on, off).
+ *   4. hysteresis: frame t is decisive when e[t] >= on (speech) or e[t] < off (silence); a frame takes the state of the latest
+ *      decisive frame u <= t, silence when there is none.
+ *   5. gap fill: a maximal silence run strictly between two speech frames with fewer than min_gap frames becomes speech (silence
+ *      that touches either end of the recording never does).
+ *   6. a speech run of fewer than min_speech frames is removed.
+ *   7. every remaining run [a, b) becomes [max(0, a - pad), min(F, b + pad)); runs that now overlap or touch are merged.
+ *   8. regions[b][i] = (first frame, one past the last), ascending, (B, cap, 2) int32: only the first cap are written; counts[b] is
+ *      the true number, <= ceil(F / 2).
+ *   Non-finite energies: the result is unspecified, but VP_OK, nothing outside the outputs is written and counts[b] <= ceil(F / 2).
+ *   0 <= offset <= onset <= 1, 0 <= floor_pct <= peak_pct <= 1, margin_db >= 0, min_gap >= 1, min_speech >= 1, pad >= 0, cap >= 0,
+ *   frame_offsets non-decreasing from a start >= 0, else VP_EINVAL.  Workspace: vp_vad_workspace_bytes(frame_offsets[B] -
+ *   frame_offsets[0], B) = 16 (total_frames / 64 + B + 1) bytes, need not be zeroed; too small: VP_EWORKSPACE.
+ * ---------------------------------------------------------------------------------------------- */
+int vp_vad_num_frames(long long n, int win, int hop);
+int vp_vad_frame_db_f32(vp_ctx* ctx, const float* wave, const int32_t* offsets, const int32_t* frame_offsets, int B, int win, int hop,
+                        float preemph, float* e, vp_stream stream);
+size_t vp_vad_workspace_bytes(long long total_frames, int B);
+int vp_vad_regions_f32(vp_ctx* ctx, const float* e, const int32_t* frame_offsets, int B, float floor_pct, float peak_pct,
+                       float margin_db, float onset, float offset, int min_gap, int min_speech, int pad, float* thr, int32_t* counts,
+                       int32_t* regions, int cap, void* ws, size_t ws_bytes, vp_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

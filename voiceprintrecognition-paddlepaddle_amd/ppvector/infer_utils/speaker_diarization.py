@@ -12,8 +12,8 @@ The Laplacian's eigenpairs have two solvers (``ppvector.set_spectral_solver``). 
 for) on the Laplacian where it was built, without copying it to the host; it is taken for 64 <= N <= 16384 windows and at most 24 wanted
 eigenvalues, and hands over to the host path (with a RuntimeWarning) when it does not converge within its caps.
 
-Voice-activity detection is NOT built: the reference uses yeaudio's model-based ``AudioSegment.vad`` (:37).  ``segments`` takes the
-speech regions from the caller instead.
+The reference's voice-activity detection is NOT built: it is yeaudio's model-based ``AudioSegment.vad`` (:37).  ``segments`` takes the
+speech regions from the caller instead -- who may get them from this project's own energy detector (``ppvector/infer_utils/vad.py``).
 """
 import math
 import warnings

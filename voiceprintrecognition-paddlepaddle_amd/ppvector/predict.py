@@ -9,8 +9,9 @@ Host bookkeeping kept in Python as in the reference: audio decoding / resampling
 as unit centroids in a device matrix (``ppvector/infer_utils/gallery.py``, docs/gallery.md) in step with the index: a query
 computes and uploads nothing but its own embedding.
 ``speaker_diarization`` (:366-396): the windows are cut, padded and normalised on the GPU from one upload of the recording, embedded
-by the same featurizer + backbone, and clustered through the pruned-affinity and Laplacian kernels (``ppvector/infer_utils``); the
-voice-activity detection in front of it is not built -- the caller passes the speech regions.
+by the same featurizer + backbone, and clustered through the pruned-affinity and Laplacian kernels (``ppvector/infer_utils``).  The
+reference's model-based voice-activity detection in front of it is not built: the caller passes the speech regions, or sets this
+project's own energy detector with ``set_vad`` (``ppvector/infer_utils/vad.py``, docs/vad.md), which finds them on the same upload.
 """
 import io
 import os
@@ -127,6 +128,7 @@ class PPVectorPredictor:
         self._cosine_threshold = None                          # the threshold in force when the score norm was set
         self.audio_db_path = audio_db_path
         self.speaker_diarize = SpeakerDiarization()
+        self._vad = None                                       # an EnergyVad: set_vad (docs/vad.md)
         if self.audio_db_path is not None:
             self.audio_indexes_path = os.path.join(audio_db_path, "audio_indexes.bin")
             self.__load_audio_db(self.audio_db_path)
@@ -321,12 +323,17 @@ class PPVectorPredictor:
         return self.users_name
 
     # ------------------------------------------------------------------ diarization
-    def chunk_embeddings(self, audio_segment, table, batch_size=32):
+    def _upload(self, audio_segment):
+        return torch.from_numpy(np.ascontiguousarray(audio_segment.samples, dtype=np.float32)).to(self.device)
+
+    def chunk_embeddings(self, audio_segment, table, batch_size=32, wave=None):
         """Embeddings (N, embd_dim) of the windows ``table`` (rows ``[start_s, end_s, first_sample, end_sample]``) of a loaded
-        recording: one upload, the windows cut / zero-padded / dB-normalised by vp_chunk_batch_f32 as ``_load_audio`` would do to each
-        of them, then the featurizer (all rows have one length: no ratio mask) and the backbone in slices of ``batch_size``."""
+        recording: one upload (``wave``: the samples already on the device, when the caller has them there), the windows cut /
+        zero-padded / dB-normalised by vp_chunk_batch_f32 as ``_load_audio`` would do to each of them, then the featurizer (all rows
+        have one length: no ratio mask) and the backbone in slices of ``batch_size``."""
         ds = self.configs.dataset_conf.dataset
-        wave = torch.from_numpy(np.ascontiguousarray(audio_segment.samples, dtype=np.float32)).to(self.device)
+        if wave is None:
+            wave = self._upload(audio_segment)
         offsets = np.asarray([[row[2], row[3]] for row in table], dtype=np.int32)
         chunks = chunk_batch(wave, offsets, self.speaker_diarize.chunk_len, normalize=bool(ds.use_dB_normalization),
                              target_db=float(ds.target_dB))
@@ -336,18 +343,55 @@ class PPVectorPredictor:
             outs.append(self.predictor(feat).cpu().numpy())
         return np.concatenate(outs, axis=0)
 
+    _NO_VAD = ('voice-activity detection (yeaudio AudioSegment.vad) is not built on the HIP engine: '
+               'pass the speech regions as vad_segments=[(start_s, end_s), ...]')
+
+    def set_vad(self, vad):
+        """An ``EnergyVad`` (no counterpart in the reference; docs/vad.md): ``speaker_diarization`` without ``vad_segments`` then takes
+        the speech regions from it.  ``set_vad(None)``, the default: such a call raises, as it always did."""
+        from ppvector.infer_utils.vad import EnergyVad
+        if vad is not None and not isinstance(vad, EnergyVad):
+            raise ValueError(f'set_vad: an EnergyVad or None, got {type(vad).__name__}')
+        self._vad = vad
+
+    def _vad_regions(self, seg, wave):
+        """The detector's regions of a loaded recording as ``segments`` can take them: it reads times to the millisecond and wants the
+        regions inside the recording and apart, so an end is rounded DOWN to the millisecond and stops where the next region starts
+        (a region ends with its last frame's window, which can reach past the first frame of a region that starts right after it)."""
+        vad = self._vad
+        if vad.sample_rate != seg.sample_rate:
+            raise ValueError(f'the detector was made for {vad.sample_rate} Hz, the recording is loaded at {seg.sample_rate} Hz')
+        regions, _ = vad.regions(wave)
+        out = []
+        for i, (start, end) in enumerate(regions):
+            if i + 1 < len(regions):
+                end = min(end, regions[i + 1][0])
+            out.append((start, int(end * 1000.0 + 1e-6) / 1000.0))     # 11.3 s is 11299.999... ms in binary
+        return out
+
+    def vad(self, audio_data, sample_rate=16000):
+        """The speech regions [(start_s, end_s)] the detector set with ``set_vad`` finds in the recording as ``_load_audio`` loads it --
+        what ``speaker_diarization`` uses when it is given no ``vad_segments``."""
+        if getattr(self, '_vad', None) is None:
+            raise NotImplementedError(self._NO_VAD)
+        seg = self._load_audio(audio_data=audio_data, sample_rate=sample_rate)
+        return self._vad_regions(seg, self._upload(seg))
+
     def speaker_diarization(self, audio_data, sample_rate=16000, speaker_num=None, search_audio_db=False, vad_segments=None):
         """说话人日志识别 -> [dict(speaker, start, end)] (predict.py:366-396).
 
         ``vad_segments``: the speech regions as (start_s, end_s) pairs, the one argument the reference does not have.  Its own
-        regions come from yeaudio's model-based ``AudioSegment.vad``, which is not built here; without ``vad_segments`` the call raises.
+        regions come from yeaudio's model-based ``AudioSegment.vad``, which is not built here; without ``vad_segments`` the call raises,
+        unless a detector was set with ``set_vad``: then the regions are that detector's, found on the upload the windows are cut from.
         """
-        if vad_segments is None:
-            raise NotImplementedError('voice-activity detection (yeaudio AudioSegment.vad) is not built on the HIP engine: '
-                                      'pass the speech regions as vad_segments=[(start_s, end_s), ...]')
+        if vad_segments is None and getattr(self, '_vad', None) is None:      # (before anything else: also on a bare instance)
+            raise NotImplementedError(self._NO_VAD)
         seg = self._load_audio(audio_data=audio_data, sample_rate=sample_rate)
+        wave = self._upload(seg)
+        if vad_segments is None:
+            vad_segments = self._vad_regions(seg, wave)
         table = self.speaker_diarize.segments(seg, vad_segments)
-        features = self.chunk_embeddings(seg, table)
+        features = self.chunk_embeddings(seg, table, wave=wave)
         labels, spk_center_embeddings = self.speaker_diarize.clustering(features, speaker_num=speaker_num)
         outputs = self.speaker_diarize.postprocess(table, labels)
         if search_audio_db:
