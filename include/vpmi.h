@@ -490,6 +490,23 @@ int vp_noise_mix_f32(vp_ctx* ctx, const float* const* srcs, const int32_t* lens,
 size_t vp_reverb_workspace_bytes(int B, int max_len, int max_rir_len);
 int vp_reverb_f32(vp_ctx* ctx, const float* const* srcs, const int32_t* lens, const float* const* rirs, const int32_t* rir_lens,
                   float* const* dsts, int B, int max_len, int max_rir_len, void* ws, size_t ws_bytes, vp_stream stream);
+/* Sample-rate conversion (AudioSegment.resample -> scipy.signal.resample_poly(x, up, down), window ('kaiser', 5.0), padtype
+ * 'constant'; call sites data_utils/reader.py:65-69 and predict.py:232-233 of this package; docs/resample.md): a ragged batch that
+ * shares one (up, down) = (rate_out, rate_in) / gcd in one launch.  With half = 10 max(up, down) and h = up * firwin(2 half + 1,
+ * 1 / max(up, down), window = ('kaiser', 5.0)), phase_table is P[p][j] = h[p + j up], [up][taps_per_phase] floats, zero where
+ * p + j up > 2 half, taps_per_phase = ceil((2 half + 1) / up); the host designs it in float64.  For m < new_lens[b], with
+ * c = m down + half (64-bit):  dsts[b][m] = sum_{j < taps_per_phase} P[c mod up][j] * srcs[b][c div up - j], a sample outside
+ * [0, lens[b]) counting as zero and never read -- one f32 fma chain in ascending j, the same bits whatever the batch.  The caller
+ * passes new_lens[b] = ceil(lens[b] up / down), resample_poly's length; nothing outside dsts[b][0 .. new_lens[b]) is written and a
+ * row with lens[b] <= 0 or new_lens[b] <= 0 is left alone.  max_new_len sizes the launch.  srcs / dsts: DEVICE arrays of B device
+ * pointers; dsts[b] must not alias srcs[b].  VP_EINVAL: a null pointer, B outside [1, 65535], max_new_len < 1, up or down outside
+ * [1, 1024], taps_per_phase not the value above.
+ * vp_resample_tile -- outputs per workgroup tile at (up, down): 1024, fewer where the table and a tile's input span would not fit the
+ * CU's LDS; 0 for a pair out of range. */
+int vp_resample_tile(int up, int down);
+int vp_resample_poly_f32(vp_ctx* ctx, const float* const* srcs, const int32_t* lens, const int32_t* new_lens,
+                         float* const* dsts, int B, int max_new_len, int up, int down, const float* phase_table,
+                         int taps_per_phase, vp_stream stream);
 
 /* ------------------------------------------------------------------------------------------------
  * ResNetSE backbone forward, eval mode -- replaces ResNetSE.forward (models/resnet_se.py:121-139) with

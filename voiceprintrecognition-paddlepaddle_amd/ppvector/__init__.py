@@ -107,6 +107,26 @@ def get_spectral_solver():
     return _SPECTRAL_SOLVER
 
 
+_RESAMPLER = 'host'
+
+
+def set_resampler(name):
+    """Where a file that is not at ``dataset_conf.dataset.sample_rate`` is converted to it (docs/resample.md):
+    'host'  scipy.signal.resample_poly on the decoding thread (``AudioSegment.resample``), as the reference does -- the default;
+    'gpu'   the same polyphase filter in HIP on the uploaded batch (csrc/resample.hip, ``data_utils/wave_batch.py`` resample_waves):
+            the dataset hands over the native-rate samples with their rate and the trainer converts them in front of the speed
+            perturbation; ``PPVectorPredictor`` uploads the native-rate recording.  The eval-mode length sort then reads the WAV
+            headers instead of decoding.  Noise and impulse-response files, and ``register``, stay on the host path."""
+    global _RESAMPLER
+    if name not in ('host', 'gpu'):
+        raise ValueError(f'unsupported resampler {name}')
+    _RESAMPLER = name
+
+
+def get_resampler():
+    return _RESAMPLER
+
+
 _TRIAL_SCORER = 'matrix'
 
 

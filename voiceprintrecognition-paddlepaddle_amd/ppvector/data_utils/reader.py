@@ -9,6 +9,13 @@ the random numbers (crop start, volume gain); everything from the dB normalisati
                               [, noise float32 (Ln,), snr_dB float, noise_start int] [, rir float32 (Lr,), unit energy])
     '.npy' list entry -> dict(feature float32 (T, F) cropped to max_feature_len (:78-83), label int)
 
+Under ppvector.set_resampler('gpu') (docs/resample.md) the workers do not resample either: `samples` are at the file's own rate and
+the item carries one more key, `sample_rate`; the trainer converts the uploaded batch (wave_batch.resample_waves).  Every length used
+here -- the min_duration check, the length after the speed change, the noise start, the crop start -- is then ceil(n up / down), the
+length resample_poly would have given, so the same seed draws the same numbers in both modes, and the eval-mode sort reads each WAV
+header's frame count instead of decoding the file.  Noise and impulse-response files keep the host conversion in both modes: the
+responses are cached after their float64 scaling and the noise level rule is stated on the decoded, resampled file.
+
 List format, min_duration skipping (:89-91), the eval-mode length sort (:121-139), train-mode random crop (yeaudio
 AudioSegment.crop: a uniform random start, 0 otherwise) follow the reference.  Speed perturbation (SpeedPerturbAugmentor:
 rate drawn from {1.0, 0.9, 1.1}, optional 3-class label offset) is drawn here and applied on the GPU; the crop start is drawn on
@@ -29,9 +36,12 @@ import os
 import random
 import threading
 
+import wave
+
 import numpy as np
 
-from ppvector.data_utils.wave_batch import SPEEDS
+import ppvector
+from ppvector.data_utils.wave_batch import SPEEDS, resample_len, resample_ratio
 from ppvector.predict import AudioSegment
 
 
@@ -64,9 +74,15 @@ class PPVectorDataset:
 
     def _decode(self, path):
         seg = AudioSegment.from_file(path)
-        if seg.sample_rate != self._target_sample_rate:
+        if seg.sample_rate != self._target_sample_rate and ppvector.get_resampler() == 'host':
             seg.resample(self._target_sample_rate)
         return seg
+
+    def _resampled_len(self, n, sample_rate):
+        """Samples an utterance of n samples at sample_rate has at the dataset's rate -- resample_poly's ceil(n up / down)."""
+        if sample_rate == self._target_sample_rate:
+            return int(n)
+        return resample_len(n, *resample_ratio(sample_rate, self._target_sample_rate))
 
     def __getitem__(self, idx):
         data_path, spk_id = self.lines[idx].strip().split('\t')
@@ -77,8 +93,12 @@ class PPVectorDataset:
                 crop_start = random.randint(0, feature.shape[0] - self.max_feature_len) if self.mode == 'train' else 0
                 feature = feature[crop_start:crop_start + self.max_feature_len, :]
             return dict(feature=np.ascontiguousarray(feature, dtype=np.float32), label=spk_id)
+        on_gpu = ppvector.get_resampler() == 'gpu'
         seg = self._decode(data_path)
-        if self.mode in ('train', 'extract_feature') and seg.duration < self.min_duration:
+        # the utterance's length at the dataset's rate: under the 'gpu' resampler the samples are still at the file's rate, and every
+        # length below is taken from this count, so that a seeded run draws the same numbers in both modes
+        n_at_rate = self._resampled_len(seg.samples.shape[0], seg.sample_rate)
+        if self.mode in ('train', 'extract_feature') and n_at_rate / float(self._target_sample_rate) < self.min_duration:
             return self.__getitem__(idx + 1 if idx < len(self.lines) - 1 else 0)
         speed, gain = 1.0, 0.0
         if self.mode == 'train' and self.speed_conf is not None and random.random() < self.speed_conf['prob']:
@@ -88,8 +108,8 @@ class PPVectorDataset:
                 spk_id = spk_id + self.num_speakers * speed_idx
         if self.mode == 'train' and self.volume_conf is not None and random.random() < self.volume_conf['prob']:
             gain = random.uniform(self.volume_conf['min_gain_dBFS'], self.volume_conf['max_gain_dBFS'])
-        n = seg.samples.shape[0] if speed == 1.0 else int(seg.samples.shape[0] / speed)      # length after the speed change
-        extra = {}
+        n = n_at_rate if speed == 1.0 else int(n_at_rate / speed)                            # length after the speed change
+        extra = dict(sample_rate=seg.sample_rate) if on_gpu else {}
         if self.mode == 'train' and self.noise_conf is not None and random.random() < self.noise_conf['prob']:
             path = random.choice(self.noise_conf['files'])
             snr = random.uniform(self.noise_conf['min_snr_dB'], self.noise_conf['max_snr_dB'])
@@ -139,6 +159,9 @@ class PPVectorDataset:
             data_path, _ = line.split('\t')
             if data_path.endswith('.npy'):
                 lengths.append(np.load(data_path, mmap_mode='r').shape[0])
+            elif ppvector.get_resampler() == 'gpu':     # the duration at the dataset's rate from the WAV header: nothing is decoded
+                with wave.open(data_path, 'rb') as w:
+                    lengths.append(self._resampled_len(w.getnframes(), w.getframerate()) / float(self._target_sample_rate))
             else:
                 lengths.append(self._decode(data_path).duration)
         self.lines = [self.lines[i] for i in np.argsort(lengths, kind='stable')]

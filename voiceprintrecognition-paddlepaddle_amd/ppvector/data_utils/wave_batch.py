@@ -1,7 +1,12 @@
 """Waveform batch assembly on the GPU -- the work PPVectorDataset.__getitem__ does per utterance on CPU workers in front
 of the featurizer (ppvector/data_utils/reader.py:97-101: decibel normalisation, crop to max_duration) plus the zero
 padding of predict_batch (ppvector/predict.py:246-254), as one launch over the whole batch (csrc/augment.hip
-wave_batch_kernel).  Decoding / resampling stay on the host; this takes the decoded utterances already on the device."""
+wave_batch_kernel).  Decoding stays on the host; this takes the decoded utterances already on the device.  Sample-rate conversion
+stays on the host too unless ppvector.set_resampler('gpu') is in force: then resample_waves (csrc/resample.hip, docs/resample.md)
+converts the uploaded native-rate utterances here, in front of everything else."""
+import threading
+from math import gcd
+
 import numpy as np
 import torch
 
@@ -160,6 +165,95 @@ def reverb_perturb(waves, rirs):
     ws = _reverb_ws.get(need, dev)
     ctx = N.ctx(dev)
     N.check(N.lib().vp_reverb_f32(ctx, sp, ld, hp, hd, dp, len(idx), max(lens), max(hlens), ws.data_ptr(), ws.numel(), N.stream_ptr()), ctx)
+    for b, w in zip(idx, dst):
+        out[b] = w
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------- sample rate
+MAX_RESAMPLE_RATE = 1024          # of max(up, down): csrc/resample.hip; a pair past it goes through the host function
+
+
+def resample_ratio(src_rate, dst_rate):
+    """(up, down) of scipy.signal.resample_poly for src_rate -> dst_rate, as AudioSegment.resample forms them."""
+    g = gcd(int(dst_rate), int(src_rate))
+    return int(dst_rate) // g, int(src_rate) // g
+
+
+def resample_len(n, up, down):
+    """resample_poly's output length for n samples: ceil(n up / down)."""
+    return -(-int(n) * int(up) // int(down))
+
+
+def resample_filter(up, down):
+    """(h float64 (2 half + 1,), half): resample_poly's default filter, up * firwin(2 half + 1, 1 / max(up, down), ('kaiser', 5.0))."""
+    from scipy.signal import firwin
+    half = 10 * max(int(up), int(down))
+    return int(up) * firwin(2 * half + 1, 1.0 / max(int(up), int(down)), window=('kaiser', 5.0)), half
+
+
+def phase_table(up, down):
+    """The kernel's coefficient table, float32 (up, J): P[p][j] = h[p + j up], zero past the filter's end, J = ceil((2 half + 1) / up).
+    Designed in float64, rounded once."""
+    h, half = resample_filter(up, down)
+    J = -(-(2 * half + 1) // int(up))
+    flat = np.zeros(J * int(up), dtype=np.float64)
+    flat[:h.shape[0]] = h
+    return np.ascontiguousarray(flat.reshape(J, int(up)).T, dtype=np.float32)
+
+
+_phase_tables, _phase_lock = {}, threading.Lock()
+
+
+def _phase_table_on(up, down, dev):
+    """phase_table(up, down) on the device, kept per (up, down, device)."""
+    key = (int(up), int(down), str(dev))
+    with _phase_lock:
+        if key not in _phase_tables:
+            _phase_tables[key] = torch.from_numpy(phase_table(up, down)).to(dev)
+        return _phase_tables[key]
+
+
+def resample_waves(waves, src_rates, dst_rate):
+    """Sample-rate conversion of a ragged batch on the GPU: row b goes from src_rates[b] to dst_rate as AudioSegment.resample does on
+    the host (scipy.signal.resample_poly(x, up, down) with its defaults; csrc/resample.hip, docs/resample.md) -- one launch per source
+    rate in the batch.  waves: list of 1-D float GPU tensors.  Returns a list: a row already at dst_rate is the SAME tensor object, a
+    converted one a new tensor of ceil(n up / down) samples.  A pair with max(up, down) > 1024 is outside the kernel's range: that
+    row takes the host function and is uploaded again."""
+    waves = [torch.as_tensor(w) for w in waves]
+    if not waves or not all(w.is_cuda for w in waves):
+        raise N.VpmiError('resample_waves takes GPU waveforms: the engine has no CPU fallback')
+    if len(src_rates) != len(waves):
+        raise ValueError(f'resample_waves: {len(src_rates)} rates for {len(waves)} utterances')
+    out = list(waves)
+    groups = {}
+    for b, r in enumerate(src_rates):
+        if int(r) != int(dst_rate):
+            groups.setdefault(resample_ratio(r, dst_rate), []).append(b)
+    for ud in [ud for ud in groups if max(ud) > MAX_RESAMPLE_RATE]:
+        from ppvector.predict import AudioSegment
+        for b in groups.pop(ud):
+            seg = AudioSegment(waves[b].reshape(-1).float().cpu().numpy(), int(src_rates[b]))
+            seg.resample(dst_rate)
+            out[b] = torch.from_numpy(seg.samples).to(waves[b].device)
+    if not groups:
+        return out
+    idx = [b for rows in groups.values() for b in rows]            # group by group: a launch's rows are neighbours in the tables
+    src = [waves[b].reshape(-1).contiguous().float() for b in idx]
+    dev = src[0].device
+    lens = [int(w.numel()) for w in src]
+    new_lens = [resample_len(n, *ud) for n, ud in zip(lens, [ud for ud, rows in groups.items() for _ in rows])]
+    dst = _ragged_empty(new_lens, dev)
+    keep, (sp, dp, ld, nd) = _device_tables(dev, [[w.data_ptr() for w in src], [w.data_ptr() for w in dst]], [lens, new_lens])
+    ctx = N.ctx(dev)
+    k0 = 0
+    for (up, down), rows in groups.items():
+        k, longest = len(rows), max(new_lens[k0:k0 + len(rows)])
+        if longest > 0:
+            table = _phase_table_on(up, down, dev)
+            N.check(N.lib().vp_resample_poly_f32(ctx, sp + 8 * k0, ld + 4 * k0, nd + 4 * k0, dp + 8 * k0, k, longest, up, down,
+                                                 table.data_ptr(), int(table.shape[1]), N.stream_ptr()), ctx)
+        k0 += k
     for b, w in zip(idx, dst):
         out[b] = w
     return out

@@ -4,7 +4,9 @@ Hot path (what runs in HIP): ``predict`` (:218-233), ``predict_batch`` (:235-269
 mask, one featurizer call, backbone in chunks), ``contrast`` (:271-283) and the 1:N search of ``recognition``
 (:173-187, :337-342) -- Fbank+CMN, backbone forward and cosine scoring all go through libvpmi.
 Host bookkeeping kept in Python as in the reference: audio decoding / resampling / dB normalisation
-(``_load_audio`` :189-216, yeaudio semantics restated for PCM WAV + ndarray input), the user index
+(``_load_audio`` :189-216, yeaudio semantics restated for PCM WAV + ndarray input; under ``ppvector.set_resampler('gpu')`` a recording
+that is not at the dataset's rate is uploaded as decoded and converted and normalised on the device instead -- ``_load_waves``,
+docs/resample.md -- in ``predict``, ``predict_batch``, ``vad`` and ``speaker_diarization``; ``register`` keeps the host path), the user index
 (pickle ``audio_indexes.bin`` with the reference's key names, :86-109).  The per-user means the search runs over (:154-164) are kept
 as unit centroids in a device matrix (``ppvector/infer_utils/gallery.py``, docs/gallery.md) in step with the index: a query
 computes and uploads nothing but its own embedding.
@@ -26,6 +28,7 @@ import yaml
 from torch import nn
 
 from ppvector.data_utils.featurizer import AudioFeaturizer
+from ppvector.data_utils.wave_batch import assemble_waves, resample_waves
 from ppvector.infer_utils.gallery import SpeakerGallery
 from ppvector.infer_utils.speaker_diarization import SpeakerDiarization, chunk_batch
 from ppvector.metric.metrics import cosine_score_matrix
@@ -215,6 +218,9 @@ class PPVectorPredictor:
 
     # ------------------------------------------------------------------ audio front end (host)
     def _load_audio(self, audio_data, sample_rate=16000):
+        return self._finish_audio(self._decode_audio(audio_data, sample_rate))
+
+    def _decode_audio(self, audio_data, sample_rate=16000):
         if isinstance(audio_data, str):
             seg = AudioSegment.from_file(audio_data)
         elif isinstance(audio_data, BufferedReader):
@@ -227,6 +233,9 @@ class PPVectorPredictor:
             seg = audio_data
         else:
             raise Exception(f'不支持该数据类型，当前数据类型为：{type(audio_data)}')
+        return seg
+
+    def _finish_audio(self, seg):
         ds = self.configs.dataset_conf.dataset
         assert seg.duration >= ds.min_duration, f'音频太短，最小应该为{ds.min_duration}s，当前音频为{seg.duration}s'
         if seg.sample_rate != ds.sample_rate:
@@ -235,27 +244,78 @@ class PPVectorPredictor:
             seg.normalize(target_db=ds.target_dB)
         return seg
 
+    def _native_segment(self, audio_data, sample_rate):
+        """(segment, audio): under the 'gpu' resampler (docs/resample.md), for input that is not at the dataset's rate, `segment` is the
+        decoded recording at its own rate, to be uploaded as it is and converted, then normalised, on the device (``_load_waves``).
+        Otherwise `segment` is None and `audio` is what ``_load_audio`` takes, to do what it always did -- the input itself under the
+        host resampler, the decoded segment for a recording that is already at the dataset's rate."""
+        import ppvector
+        if ppvector.get_resampler() != 'gpu':
+            return None, audio_data
+        seg = self._decode_audio(audio_data, sample_rate)
+        return (seg, None) if seg.sample_rate != self.configs.dataset_conf.dataset.sample_rate else (None, seg)
+
+    def _load_waves(self, segs):
+        """What ``_finish_audio`` does to native-rate segments, on the device: the duration check, one upload each at the file's rate,
+        resample_waves, then the dB normalisation over the whole converted recording by vp_wave_batch_f32.  Returns
+        ((len(segs), L) f32 rows zero-padded to the longest, [samples of each row])."""
+        ds = self.configs.dataset_conf.dataset
+        for seg in segs:
+            assert seg.duration >= ds.min_duration, f'音频太短，最小应该为{ds.min_duration}s，当前音频为{seg.duration}s'
+        waves = resample_waves([self._upload(seg) for seg in segs], [seg.sample_rate for seg in segs], ds.sample_rate)
+        batch, _ = assemble_waves(waves, use_dB_normalization=bool(ds.use_dB_normalization), target_dB=float(ds.target_dB))
+        return batch, [int(w.numel()) for w in waves]
+
+    def _load_recording(self, audio_data, sample_rate):
+        """(segment, samples on the device) of a whole recording for ``vad`` / ``speaker_diarization``.  Converted on the device, the
+        segment is a stand-in at the dataset's rate whose ``samples`` have the converted length and no storage: the chunk table reads
+        only lengths, and no host copy of the converted recording is made."""
+        native, audio_data = self._native_segment(audio_data, sample_rate)
+        if native is None:
+            seg = self._load_audio(audio_data=audio_data, sample_rate=sample_rate)
+            return seg, self._upload(seg)
+        batch, (n,) = self._load_waves([native])
+        stand_in = AudioSegment.__new__(AudioSegment)           # (the constructor would copy the samples)
+        stand_in.samples = np.broadcast_to(np.float32(0.0), (n,))
+        stand_in.sample_rate = int(self.configs.dataset_conf.dataset.sample_rate)
+        return stand_in, batch[0]
+
     # ------------------------------------------------------------------ hot path
     def predict(self, audio_data, sample_rate=16000):
         """预测一个音频的特征 -> (embd_dim,) float32."""
-        seg = self._load_audio(audio_data=audio_data, sample_rate=sample_rate)
-        x = torch.from_numpy(seg.samples).to(self.device).unsqueeze(0)
+        native, audio_data = self._native_segment(audio_data, sample_rate)
+        if native is not None:
+            x, _ = self._load_waves([native])
+        else:
+            seg = self._load_audio(audio_data=audio_data, sample_rate=sample_rate)
+            x = torch.from_numpy(seg.samples).to(self.device).unsqueeze(0)
         feat = self._audio_featurizer(x, want_bf16=self._want_bf16())
         return self.predictor(feat).cpu().numpy()[0]
 
     def predict_batch(self, audios_data, sample_rate=16000, batch_size=32):
         """预测一批音频的特征: zero-pad the WAVEFORMS to the longest, ratio mask, as the reference does."""
-        waves = [self._load_audio(audio_data=a, sample_rate=sample_rate).samples for a in audios_data]
-        longest = max(w.shape[0] for w in waves)
+        native, audios_data = zip(*[self._native_segment(a, sample_rate) for a in audios_data])
+        on_gpu = [i for i, s in enumerate(native) if s is not None]
+        host = [i for i, s in enumerate(native) if s is None]
+        waves = [self._load_audio(audio_data=audios_data[i], sample_rate=sample_rate).samples for i in host]
+        converted, lens = self._load_waves([native[i] for i in on_gpu]) if on_gpu else (None, [])
+        longest = max([w.shape[0] for w in waves] + lens)
         inputs = np.zeros((len(waves), longest), dtype=np.float32)
-        ratios = []
-        for i, w in enumerate(waves):
-            inputs[i, :w.shape[0]] = w
-            ratios.append(w.shape[0] / longest)
+        ratios = [0.0] * len(native)
+        for k, (i, w) in enumerate(zip(host, waves)):
+            inputs[k, :w.shape[0]] = w
+            ratios[i] = w.shape[0] / longest
         x = torch.from_numpy(inputs).to(self.device)
+        if on_gpu:                                             # the rows converted on the device, zero-padded, among the others
+            rows = torch.zeros((len(native), longest), dtype=torch.float32, device=self.device)
+            rows[torch.tensor(host, dtype=torch.int64, device=self.device)] = x
+            rows[torch.tensor(on_gpu, dtype=torch.int64, device=self.device), :converted.shape[1]] = converted
+            x = rows
+            for i, n in zip(on_gpu, lens):
+                ratios[i] = n / longest
         r = torch.tensor(ratios, dtype=torch.float32, device=self.device)
         feat = self._audio_featurizer(x, r)
-        outs = [self.predictor(feat[i:i + batch_size].contiguous()).cpu().numpy() for i in range(0, len(waves), batch_size)]
+        outs = [self.predictor(feat[i:i + batch_size].contiguous()).cpu().numpy() for i in range(0, len(native), batch_size)]
         return np.concatenate(outs, axis=0)
 
     def contrast(self, audio_data1, audio_data2):
@@ -374,8 +434,8 @@ class PPVectorPredictor:
         what ``speaker_diarization`` uses when it is given no ``vad_segments``."""
         if getattr(self, '_vad', None) is None:
             raise NotImplementedError(self._NO_VAD)
-        seg = self._load_audio(audio_data=audio_data, sample_rate=sample_rate)
-        return self._vad_regions(seg, self._upload(seg))
+        seg, wave = self._load_recording(audio_data, sample_rate)
+        return self._vad_regions(seg, wave)
 
     def speaker_diarization(self, audio_data, sample_rate=16000, speaker_num=None, search_audio_db=False, vad_segments=None):
         """说话人日志识别 -> [dict(speaker, start, end)] (predict.py:366-396).
@@ -386,8 +446,7 @@ class PPVectorPredictor:
         """
         if vad_segments is None and getattr(self, '_vad', None) is None:      # (before anything else: also on a bare instance)
             raise NotImplementedError(self._NO_VAD)
-        seg = self._load_audio(audio_data=audio_data, sample_rate=sample_rate)
-        wave = self._upload(seg)
+        seg, wave = self._load_recording(audio_data, sample_rate)
         if vad_segments is None:
             vad_segments = self._vad_regions(seg, wave)
         table = self.speaker_diarize.segments(seg, vad_segments)

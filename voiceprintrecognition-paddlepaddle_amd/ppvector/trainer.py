@@ -5,7 +5,7 @@
 What moved: the reference builds features one utterance at a time on CPU DataLoader workers (reader.py:72-109) and feeds
 (B, T, F) tensors to the device; here worker THREADS only decode audio, and one step is
 
-    decoded waves --H2D--> speed_perturb -> noise_perturb -> reverb_perturb -> assemble_waves (dB normalise, crop, pad: 1 launch)
+    decoded waves --H2D--> [resample_waves] -> speed_perturb -> noise_perturb -> reverb_perturb -> assemble_waves (dB normalise, crop, pad: 1 launch)
       -> AudioFeaturizer (Fbank / Mel + CMN)
       -> SpecAugmentor.batch -> nn.Sequential(backbone, classifier) train-mode forward -> criterion -> backward
       -> bucketed gradient all-reduce over RCCL (one process per GPU, torch.distributed) -> flat Adam step
@@ -32,7 +32,7 @@ from torch import nn
 
 from ppvector.data_utils.featurizer import AudioFeaturizer
 from ppvector.data_utils.reader import PPVectorDataset
-from ppvector.data_utils.wave_batch import assemble_waves, noise_perturb, reverb_perturb, speed_perturb
+from ppvector.data_utils.wave_batch import assemble_waves, noise_perturb, resample_waves, reverb_perturb, speed_perturb
 from ppvector.loss import build_loss
 from ppvector.metric.metrics import evaluate_trials
 from ppvector.models import build_model
@@ -152,6 +152,9 @@ class PPVectorTrainer(object):
             feats, _, _ = collate_fn([(torch.from_numpy(it['feature']).to(self.device), it['label']) for it in items])
             return feats, labels
         waves = self._upload([it['samples'] for it in items])
+        if any('sample_rate' in it for it in items):            # the 'gpu' resampler: the samples came at their files' rates
+            rate = dataset._target_sample_rate
+            waves = resample_waves(waves, [it.get('sample_rate', rate) for it in items], rate)
         waves = speed_perturb(waves, [it.get('speed', 1.0) for it in items])
         # noise, then reverb, on the utterances the reader selected (train mode only: eval / extract_feature items carry no such keys),
         # in the reference's order (reader.py:159-162) and in front of the normalisation, which must see the augmented signal's level
