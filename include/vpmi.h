@@ -234,7 +234,8 @@ int vp_dense_f32(vp_ctx* ctx, const float* a, int lda, const float* w, int w_is_
 int vp_cast_f32_bf16(vp_ctx* ctx, const float* x, void* y, long long n, vp_stream stream);
 
 
-/* SE gate applied + residual: out = x * s[b, c] + res  (ecapa_tdnn.py:82 and :142). */
+/* SE gate applied + residual: out = x * s[b, c] + res  (ecapa_tdnn.py:82 and :142).  C, the leading dimensions and the offsets are
+ * multiples of 4 (f32), 8 (bf16) or 32 (VP_HL32); x, s, res and out are 16-byte aligned (VP_EINVAL otherwise, nothing launched). */
 int vp_se_scale_residual(vp_ctx* ctx, int dtype, const void* x, int ldx, int xoff, const float* s,
                          const void* res, int ldr, int roff, void* out, int ldo, int ooff,
                          int B, int T, int C, vp_stream stream);

@@ -322,6 +322,8 @@ static int se_scale_residual_impl(vp_ctx* ctx, int dtype, const void* x, int ldx
     const int V = dtype == VP_HL32 ? 32 : dtype == VP_BF16 ? 8 : 4;
     if (C % V || ldx % V || xoff % V || ldr % V || roff % V || ldo % V || ooff % V)
         VP_FAIL(ctx, VP_EINVAL, "se: C/ld/off must be multiples of %d", V);
+    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(res) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(s)) & 15)
+        VP_FAIL(ctx, VP_EINVAL, "se: tensors must be 16-byte aligned");              // every flavour moves 16-byte vectors
     if (dtype == VP_HL32) {
         const long long tot = (long long)B * T * (C / 8);
         long long nb = (tot + 255) / 256;
@@ -513,7 +515,8 @@ __global__ __launch_bounds__(1024) void se_gate_kernel(SeGateArgs a) {
                     s1 += a.psum[((size_t)tm * a.nseg + seg) * a.C + c2];
                 }
             }
-            if (groups == 1) mean[i2] = (a.shift ? a.shift[c2] : 0.f) + s1 / (float)a.T;
+            // groups == 1 with C < blockDim: the threads past C have gq >= 1, summed nothing and must not write (their i2 aliases a live channel)
+            if (groups == 1) { if (gq == 0) mean[i2] = (a.shift ? a.shift[c2] : 0.f) + s1 / (float)a.T; }
             else if (gq < groups) part[gq * (SE_UPW * a.C) + i2] = s1;
             (void)u2;
         }
