@@ -1266,6 +1266,34 @@ int vp_vad_regions_f32(vp_ctx* ctx, const float* e, const int32_t* frame_offsets
                        float margin_db, float onset, float offset, int min_gap, int min_speech, int pad, float* thr, int32_t* counts,
                        int32_t* regions, int cap, void* ws, size_t ws_bytes, vp_stream stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Score calibration (csrc/calibrate.hip, docs/calibration.md).  No reference call site: an extension -- the reference has no
+ * calibrated score.  The affine calibration llr = a s + b is a logistic regression over all Nt Ne pairs of the trial scorer above;
+ * these entry points give, for one (a, b), the twelve float64 sums from which the host takes the objective, its gradient and its
+ * Hessian.  Nothing of size Nt Ne is written.  The pairs, their classes and their scores are the trial scorer's: ws is the
+ * workspace a vp_trial_ranks_targets_f32 (or _norm_f32) call on the same lists left its unit rows in, trial_ids / enroll_ids the
+ * labels it was given; a pair is a target when the two ids are equal.
+ * vp_trial_calib_partials_bytes -- no reference call site: an extension.  96 bytes per workgroup of the pass; 0 for a shape
+ *   vp_trial_ranks_workspace_bytes refuses whatever NT is (Nt, Ne >= 1, D % 4 == 0, D <= 1024).
+ * vp_trial_calib_sums_f32 -- no reference call site: an extension.  ab: TWO doubles ON THE HOST, a and b (b includes the prior's
+ *   log odds).  With s the pair's cosine widened to float64, y = a s + b (two operations, each rounded), u = -y for a target and
+ *   +y for a non-target, e = exp(-|u|), sigma(u) = 1 / (1 + e) for u >= 0 and e / (1 + e) otherwise, softplus(u) = max(u, 0) +
+ *   log1p(e), w = sigma(u) sigma(-u):  sums[0 .. 5] = sum over the targets of softplus(u), sigma(u), sigma(u) s, w, w s, w s s;
+ *   sums[6 .. 11] the same over the non-targets.  sums: 12 doubles on the device.  Every term and every sum is float64, added in
+ *   an order the shape alone fixes (lanes of a wave, waves of a workgroup, then the workgroups' partials in index order by a second
+ *   kernel of one workgroup): no float atomics, no grid barrier, no spinning; two runs give the same bits.  partials need not be
+ *   cleared.  Checked before anything touches a device, in this order: an unsupported shape is VP_EUNSUP; a null pointer, a
+ *   non-finite a or b, a workspace below vp_trial_ranks_workspace_bytes or partials below vp_trial_calib_partials_bytes: VP_EINVAL.
+ * vp_trial_calib_sums_norm_f32 -- no reference call site: an extension.  The same with s = z of the cosine (score normalisation
+ *   above), from the four statistics arrays in the order the _norm rank passes take them.
+ * ---------------------------------------------------------------------------------------------- */
+size_t vp_trial_calib_partials_bytes(int Nt, int Ne, int D);
+int vp_trial_calib_sums_f32(vp_ctx* ctx, const int* trial_ids, int Nt, const int* enroll_ids, int Ne, int D, const double* ab,
+                            double* sums, void* partials, size_t partials_bytes, const void* ws, size_t ws_bytes, vp_stream stream);
+int vp_trial_calib_sums_norm_f32(vp_ctx* ctx, const int* trial_ids, int Nt, const int* enroll_ids, int Ne, int D, const double* ab,
+                                 double* sums, void* partials, size_t partials_bytes, const float* trial_mean, const float* trial_r,
+                                 const float* enroll_mean, const float* enroll_r, const void* ws, size_t ws_bytes, vp_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

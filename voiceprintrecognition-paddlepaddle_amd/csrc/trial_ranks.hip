@@ -17,6 +17,7 @@
 // vp_trial_ranks_*_norm_f32 entry points; NORM = false is the cosine itself.
 #include "cos_tile.h"
 #include "score_norm.h"
+#include "trial_plan.h"
 
 namespace {
 
@@ -27,12 +28,11 @@ constexpr long long MAX_NT = 1LL << 24;
 constexpr int MAX_LDS = 160 * 1024;
 constexpr int PIVOTS = 2048;            // two-level search: at most this many pivots in LDS
 constexpr int DIGIT_BINS = 2048;
-constexpr int MAX_SLABS_PER_WG = 1 << 16;       // 32 x 128 x 2^16 = 2^28 pairs per workgroup: a 32-bit LDS count cannot wrap
 
 enum { TARGETS = 0, COUNTS = 1, SELECT = 2 };
 
 bool supported(int Nt, int Ne, int D, long long NT) {
-    return Nt >= 1 && Ne >= 1 && D >= 4 && D % 4 == 0 && D <= MAX_D && NT >= 1 && NT <= MAX_NT;
+    return trial_plan::shape_ok(Nt, Ne, D) && NT >= 1 && NT <= MAX_NT;
 }
 
 struct Plan {
@@ -43,19 +43,11 @@ struct Plan {
 
 Plan plan(int Nt, int Ne, int D, long long NT) {
     Plan p{};
-    p.qtiles = (Nt + QT - 1) / QT;
-    const int slabs = (Ne + SLAB - 1) / SLAB;
-    // about a thousand workgroups where the shape has them; a workgroup walks at least two slabs (its tile is loaded once)
-    const int want = (1024 + p.qtiles - 1) / p.qtiles;
-    int spw = (slabs + want - 1) / want;
-    const int least = slabs < 2 ? slabs : 2, by_grid = (slabs + 65534) / 65535;
-    spw = spw > least ? spw : least;
-    spw = spw > by_grid ? spw : by_grid;
-    spw = spw < MAX_SLABS_PER_WG ? spw : MAX_SLABS_PER_WG;
-    p.slabs_per_wg = spw;
-    p.ranges = (slabs + spw - 1) / spw;
-    const int Dp = (D + 7) / 8 * 8;
-    p.tile_lds = (size_t)Dp * QT * 4;
+    const trial_plan::Walk w = trial_plan::walk(Nt, Ne, D);
+    p.qtiles = w.qtiles;
+    p.slabs_per_wg = w.slabs_per_wg;
+    p.ranges = w.ranges;
+    p.tile_lds = w.tile_lds;
     const size_t room = (MAX_LDS - p.tile_lds) / 4;         // words beside the tile: >= 8192
     if ((size_t)(2 * NT + 1) <= room) {
         p.stride = 1;
@@ -68,8 +60,8 @@ Plan plan(int Nt, int Ne, int D, long long NT) {
         p.H = (size_t)(NT + 1) < h ? (int)(NT + 1) : (int)h;
     }
     p.count_lds = p.tile_lds + ((size_t)p.P + p.H) * 4;
-    p.unit_t = vp_align_up((size_t)Nt * D * 4, 256);
-    p.bytes = p.unit_t + vp_align_up((size_t)Ne * D * 4, 256);
+    p.unit_t = w.unit_t;
+    p.bytes = w.bytes;
     return p;
 }
 

@@ -7,7 +7,7 @@ import re
 from types import SimpleNamespace
 
 SCALARS = {'int': C.c_int, 'int32_t': C.c_int, 'float': C.c_float, 'size_t': C.c_size_t, 'long long': C.c_longlong}
-POINTEES = {'void', 'char', 'float', 'int', 'int16_t', 'int32_t', 'int64_t', 'long long'}     # T* -> c_void_p
+POINTEES = {'void', 'char', 'float', 'double', 'int', 'int16_t', 'int32_t', 'int64_t', 'long long'}     # T* -> c_void_p
 TYPE = r'(?:const\s+)?(long long|\w+)\s*((?:\*\s*(?:const\s*)?)*)'                            # base type, then its stars
 
 

@@ -182,6 +182,26 @@ class TrialRanks:
         bits = key ^ 0x80000000 if key >> 31 else key ^ 0xffffffff
         return float(np.asarray([bits], np.uint32).view(np.float32)[0])
 
+    def calib_sums(self, a, b):
+        """The twelve float64 sums of the calibration objective at llr + tau = a s + b over all pairs (csrc/calibrate.hip,
+        docs/calibration.md) -> ndarray (2, 6) float64, targets first: sum of softplus(u), sigma(u), sigma(u) s, w, w s, w s^2.
+        One pass over the unit rows this object's workspace holds and one 96-byte read-back; s is z when a score norm was given."""
+        import ctypes
+        import torch
+        from ppvector import _native as N
+        if getattr(self, '_calib_partials', None) is None:
+            need = self._lib.vp_trial_calib_partials_bytes(self.Nt, self.Ne, self.D)
+            self._calib_partials = torch.empty(need, dtype=torch.uint8, device=self._dev)
+            self._calib_out = torch.empty(12, dtype=torch.float64, device=self._dev)
+        ab = (ctypes.c_double * 2)(float(a), float(b))
+        stats = () if self.stats is None else tuple(t.data_ptr() for t in self.stats)
+        sums_pass = self._lib.vp_trial_calib_sums_f32 if self.stats is None else self._lib.vp_trial_calib_sums_norm_f32
+        with torch.cuda.device(self._dev):
+            N.check(sums_pass(self._ctx, self._tl.data_ptr(), self.Nt, self._el.data_ptr(), self.Ne, self.D,
+                              ctypes.addressof(ab), self._calib_out.data_ptr(), self._calib_partials.data_ptr(),
+                              self._calib_partials.numel(), *stats, self._ws.data_ptr(), self._ws.numel(), N.stream_ptr()), self._ctx)
+        return self._calib_out.cpu().numpy().reshape(2, 6)
+
 
 def trial_ranks(trials, trial_labels, enroll, enroll_labels):
     """(Nt, D), (Ne, D) GPU tensors and their labels -> (targets float32 (NT,) ascending, hist int64 (NT + 1,)), NumPy arrays: the

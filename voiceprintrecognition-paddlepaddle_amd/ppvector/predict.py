@@ -129,6 +129,7 @@ class PPVectorPredictor:
         self.gallery = None                                    # SpeakerGallery, made with the first enrolled embedding's width
         self.score_norm = None                                 # a ScoreNorm: set_score_norm (docs/gallery.md)
         self._cosine_threshold = None                          # the threshold in force when the score norm was set
+        self.calibration = None                                # a Calibration: set_calibration (docs/calibration.md)
         self.audio_db_path = audio_db_path
         self.speaker_diarize = SpeakerDiarization()
         self._vad = None                                       # an EnergyVad: set_vad (docs/vad.md)
@@ -326,6 +327,34 @@ class PPVectorPredictor:
         if self.score_norm is not None:
             s = self.score_norm.normalise(s.contiguous(), a, b)
         return float(s[0, 0])
+
+    # ------------------------------------------------------------------ calibrated pair scores (docs/calibration.md)
+    def set_calibration(self, calibration):
+        """A ``Calibration``, the path of one saved as JSON, or None (no counterpart in the reference): what ``contrast_llr`` and
+        ``contrast_probability`` map the pair score with.  ``contrast``, ``recognition*`` and ``register`` do not look at it."""
+        from ppvector.metric.calibration import Calibration
+        if isinstance(calibration, (str, os.PathLike)):
+            calibration = Calibration.load(calibration)
+        if calibration is not None and not isinstance(calibration, Calibration):
+            raise ValueError(f'set_calibration: a Calibration, a path or None, got {type(calibration).__name__}')
+        self.calibration = calibration
+
+    def _calibration(self, what):
+        cal = self.calibration
+        if cal is None:
+            raise ValueError(f'{what}: no calibration is set (set_calibration)')
+        if cal.normalised != (self.score_norm is not None):
+            raise ValueError(f'{what}: the calibration was fitted on {"normalised scores" if cal.normalised else "raw cosines"}, '
+                             f'and a score norm is {"not set" if self.score_norm is None else "set"}')
+        return cal
+
+    def contrast_llr(self, audio_data1, audio_data2):
+        """The log-likelihood ratio (natural log) of "same speaker" for the pair: a s + b of the score ``contrast`` returns."""
+        return self._calibration('contrast_llr').llr(self.contrast(audio_data1, audio_data2))
+
+    def contrast_probability(self, audio_data1, audio_data2, p_target=0.5):
+        """The posterior probability of "same speaker" for the pair, for a target prior p_target."""
+        return self._calibration('contrast_probability').posterior(self.contrast(audio_data1, audio_data2), p_target=p_target)
 
     def _want_bf16(self):
         import ppvector

@@ -115,6 +115,7 @@ class PPVectorTrainer(object):
         self.train_loss, self.train_acc = None, None
         self.train_eta_sec = None
         self.eval_eer, self.eval_min_dcf, self.eval_threshold = None, None, None
+        self.eval_cllr, self.eval_min_cllr = None, None         # set by calibrate() (docs/calibration.md)
         self.test_log_step, self.train_log_step = 0, 0
         self.stop_train, self.stop_eval = False, False
 
@@ -375,8 +376,9 @@ class PPVectorTrainer(object):
                 labels.append(y)
         return (torch.cat(feats), torch.cat(labels)) if feats else (None, None)
 
-    def evaluate(self, resume_model=None, save_image_path=None):
-        """-> (eer, min_dcf, threshold) floats, or (-1, -1, -1) when stop_eval was raised (trainer.py:367-447)."""
+    def _eval_embeddings(self, resume_model=None):
+        """The embedding half of evaluate() and calibrate(): loaders and model set up on first use, the checkpoint loaded, the enrol
+        and the trial list embedded in eval mode -> (enrol features, enrol labels, trial features, trial labels), device tensors."""
         if self.enroll_loader is None or self.trials_loader is None:
             self.__setup_dataloader()
         if self.model is None:
@@ -391,6 +393,11 @@ class PPVectorTrainer(object):
         enroll_features, enroll_labels = self._embed(self.enroll_loader, self.enroll_dataset, eval_model)
         trials_features, trials_labels = self._embed(self.trials_loader, self.trials_dataset, eval_model)
         self.model.train()
+        return enroll_features, enroll_labels, trials_features, trials_labels
+
+    def evaluate(self, resume_model=None, save_image_path=None):
+        """-> (eer, min_dcf, threshold) floats, or (-1, -1, -1) when stop_eval was raised (trainer.py:367-447)."""
+        enroll_features, enroll_labels, trials_features, trials_labels = self._eval_embeddings(resume_model)
         if self.stop_eval:
             return -1, -1, -1
         eer, min_dcf, threshold = evaluate_trials(enroll_features, enroll_labels.cpu().numpy(), trials_features,
@@ -398,6 +405,24 @@ class PPVectorTrainer(object):
         if save_image_path:
             _LOG.warning('save_image_path: the fnr/fpr plot (matplotlib) is not produced by this build')
         return float(eer), float(min_dcf), float(threshold)
+
+    # ------------------------------------------------------------------------------------------------ calibration
+    # An extension (docs/calibration.md; the reference has no calibrated score).  Opt-in: evaluate() and train() never call it.
+    def calibrate(self, resume_model=None, save_path=None, prior=0.5):
+        """Fits llr = a s + b on the scores evaluate() ranks -- the enrol and the trial list, embedded as evaluate() embeds them and
+        scored with the configured score normalisation, if any -> Calibration, written as JSON when save_path is given; None when
+        stop_eval was raised.  Sets eval_cllr (the cost of the fitted LLRs) and eval_min_cllr (the ranking's floor)."""
+        from ppvector.metric.calibration import fit_calibration
+        enroll_features, enroll_labels, trials_features, trials_labels = self._eval_embeddings(resume_model)
+        if self.stop_eval:
+            return None
+        cal, info = fit_calibration(enroll_features, enroll_labels.cpu().numpy(), trials_features, trials_labels.cpu().numpy(),
+                                    prior=prior, score_norm=self._score_norm())
+        self.eval_cllr, self.eval_min_cllr = info['cllr'], info['min_cllr']
+        if save_path:
+            os.makedirs(os.path.dirname(os.path.abspath(save_path)), exist_ok=True)
+            cal.save(save_path)
+        return cal
 
     # ------------------------------------------------------------------------------------------------ score normalisation
     # An extension (docs/score_norm.md; the reference evaluates raw cosines only): dataset_conf.eval_conf.score_norm =
